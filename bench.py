@@ -28,6 +28,9 @@ Rank 0 prints ONE COMPACT JSON line (< 3 KB: the driver keeps an 8-KB tail of st
 Everything else -- the full per-stage roofline list, every leg (--legs all: fp16 everywhere, ref_split, ref_split_fp32mfma,
 attn_mfma16, vit_small, config5, natural), --include-h2d (PCIe-inclusive), --precision (errors vs the oracle
 outputs of the same run) -- goes to gpurun_out/bench_detail.json (--detail PATH) and is summarised on stderr.
+
+``--dump-outputs DIR`` writes the outputs of the last timed step as DIR/<name>.npy (dump_outputs: at most 64 MB, a seeded
+sample of the larger ones); the inputs are seeded, so two builds run with the same arguments can be compared file by file.
 """
 import argparse
 import json
@@ -302,8 +305,8 @@ def cpu_baseline(cfg, sd):
                          "threads, 250 s on all 256).  The only "
                          "reference-side measurement is the survey's: the reference module itself, 0.055 pairs/s on the 8 cores "
                          "of the build container (BASELINE.md section 2)",
-            "pinned_by": "tests/test_oracle_golden.py (the oracle vs the reference's own outputs, tests/golden/*.npz, regenerated "
-                         "from /root/reference by oracle/make_golden.py in test_committed_fixtures_reproduce_from_the_reference)",
+            "pinned_by": "tests/test_oracle_golden.py (the oracle vs the reference's own outputs, tests/golden/*.npz, written "
+                         "from the reference by oracle/make_golden.py)",
             "protocol": "1 warm-up + 3 timed runs, the median counts", "stage_seconds": {k: round(v, 4) for k, v in med.items()},
             "runs_total_seconds": [round(r["total"], 4) for r in runs], "threads_probe": probe,
             "sample": "1 pair 540x720, full forward (ViT-L fp32 + heads + dual-softmax + 20x100 RANSAC), torch-CPU "
@@ -402,12 +405,17 @@ def parse_args(argv=None):
                     help="hipGraph replay of the forward (auto: batches of <= 4 pairs, where launches dominate)")
     ap.add_argument("--dump-poses", default=None, help="TEST HOOK (tests/test_rccl_gpu.py): torch.save the poses of the last "
                                                         "timed step (the gathered ones under torch.distributed.run) to this path")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / float64, at most 64 MB in all: "
+                         "a fixed seeded sample of the larger outputs), so that two builds can be compared output for output")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend ('nccl' is RCCL on ROCm)")
     ap.add_argument("--stub", action="store_true",
                     help="TEST HOOK (tests/test_bench_cpu.py): CPU tensors and a trivial stand-in model, so that the launcher, "
                          "sharding, gather and timing logic of --gpus N can be exercised under gloo without a GPU; "
                          "the printed line is marked \"stub\": true and is not a measurement")
     args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
     args.sustained = not args.no_sustained
     if args.lean:
         args.no_single = args.no_cpu_baseline = True
@@ -515,6 +523,46 @@ def measure(model, data0, args, use_dist, world, gatherer, prof=None):
     return dt, last, poses
 
 
+DUMP_BYTES = 64 * 10**6   # --dump-outputs: every .npy file together, headers included
+NPY_HEADER = 128          # bytes np.save puts before the data of an array of up to a few dimensions
+
+
+def dump_outputs(data, out_dir, inputs=(), budget=DUMP_BYTES, seed=0):
+    """--dump-outputs: every tensor of `data` (the dict the timed forward filled) except the `inputs`, as <out_dir>/<name>.npy:
+    float64 for float64 and 32 / 64-bit integer tensors (exact), float32 otherwise.  Written smallest first, each whole when
+    it fits an even share of what is left of the budget; a larger one becomes a 1-D sample of that many elements at sorted
+    flat indices drawn from a generator seeded with `seed`, so that the same shapes give the same sample on every run.
+    -> {name: [shape, elements written]}"""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    items = sorted(((k, v) for k, v in data.items() if torch.is_tensor(v) and k not in inputs), key=lambda kv: (kv[1].numel(), kv[0]))
+    left = budget - NPY_HEADER * len(items)
+    written = {}
+    for i, (name, v) in enumerate(items):
+        wide = v.dtype == torch.float64 or (not v.is_floating_point() and v.element_size() >= 4)
+        itemsize = 8 if wide else 4
+        n = min(v.numel(), left // (len(items) - i) // itemsize)
+        flat = v.detach().reshape(-1)
+        if n < v.numel():
+            idx = torch.randint(v.numel(), (n,), generator=torch.Generator().manual_seed(seed)).sort().values
+            flat = flat[idx.to(flat.device)]
+        arr = flat.to(torch.float64 if wide else torch.float32).cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), arr.reshape(tuple(v.shape)) if n == v.numel() else arr)
+        left -= n * itemsize
+        written[name] = [list(v.shape), n]
+    return written
+
+
+def dump_last_step(out_dir, last, poses, data0):
+    """--dump-outputs of measure()'s last step: with N > 1 ranks R, t and inliers are the gathered poses of the whole batch
+    (what a caller of the sharded forward receives), the other outputs rank 0's shard."""
+    out = dict(last)
+    if poses is not None:
+        out.update(R=poses[0], t=poses[1], inliers=poses[2])
+    dump_outputs(out, out_dir, inputs=set(data0))
+
+
 def per_rank_ms(steps):
     """min / max / all of the ranks' own ms per step of the last measure() (the first thing to look at when a scaling run
     disappoints: one slow rank, or all of them)."""
@@ -563,6 +611,8 @@ def main_stub(args, rank, world, use_dist):
         assert poses is not None and poses[0].shape[0] == world * B, "gathered poses do not cover the global batch"
         # every rank's own poses sit at its slot of the gathered batch
         assert torch.equal(poses[0][rank * B:(rank + 1) * B], last["R"])
+    if args.dump_outputs and rank == 0:
+        dump_last_step(args.dump_outputs, last, poses, data0)
     if rank == 0:
         print(json.dumps({"metric": "image pairs/sec (540x720)", "stub": True, "value": world * B * args.steps / dt,
                           "unit": "pairs/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -691,6 +741,9 @@ def main(argv=None):
     dt, last, poses = measure(model, data0, args, use_dist, world, gatherer, prof)
     if rank == 0:
         tick("headline measured")
+    if args.dump_outputs and rank == 0:
+        # now, before anything else runs the model: eager-mode outputs are views of its workspace
+        dump_last_step(args.dump_outputs, last, poses, data0)
     graphed = len(model._graphs) > 0
     ev_steps = args.steps
     if graphed and prof is not None:

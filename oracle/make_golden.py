@@ -189,9 +189,38 @@ def golden_submission_lines():
     print("submission_lines: %d lines, e.g. %s" % (len(lines), lines[0]))
 
 
+def gold_mapfree_records():
+    """tests/golden/mapfree_records.npz: what the REFERENCE's MapFreeScene (lib/datasets/mapfree.py) yields over the tiny
+    Map-free dataset of tests/helpers/tiny_mapfree.py, read at the stored size and at a larger model size.  The reference
+    runs in a subprocess (tests/helpers/run_reference_dataset.py) with its root first on PYTHONPATH: its `lib.datasets`."""
+    import json
+    import subprocess
+    import tempfile
+    from tests.helpers import tiny_mapfree
+    print("[mapfree_records] reference MapFreeScene over tiny_mapfree")
+    queries, factor, size, size2 = 12, 5, (126, 168), (270, 360)
+
+    def run(split_root, W, H):
+        env = dict(os.environ, PYTHONPATH=ref_shim.REF_ROOT + os.pathsep + ROOT)
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "helpers", "run_reference_dataset.py"), split_root,
+                            str(W), str(H), str(factor)], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, env=env,
+                           timeout=600)
+        assert r.returncode == 0, r.stdout[-3000:]
+        return json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("RESULT ")][-1][7:])
+
+    with tempfile.TemporaryDirectory() as tmp:
+        split_root = tiny_mapfree.make(tmp, "test", queries=queries, size=size)
+        ref, ref2 = run(split_root, *size), run(split_root, *size2)
+    np.savez(os.path.join(GOLD, "mapfree_records.npz"), queries=queries, factor=factor, size=size, size2=size2,
+             scene_id=np.array([b["scene_id"] for b in ref]), pair_names=np.array([b["pair_names"] for b in ref]),
+             Kori_color0=np.array([b["Kori_color0"] for b in ref], dtype=np.float32),
+             image0_shape=np.array([b["image0_shape"] for b in ref]), image0_sum=np.array([b["image0_sum"] for b in ref]),
+             K_color0_size2=np.array([b["K_color0"] for b in ref2], dtype=np.float32))
+    print("  wrote mapfree_records.npz (%d records)" % len(ref))
+
+
 def main(out_dir=None):
-    """out_dir: write the fixtures somewhere else (tests/test_oracle_golden.py regenerates them into a temp dir and
-    compares with the committed ones)."""
+    """out_dir: write the fixtures somewhere else (to compare a regeneration with the committed ones)."""
     global GOLD
     if out_dir is not None:
         GOLD = out_dir
@@ -204,6 +233,7 @@ def main(out_dir=None):
     gold_solver(cfg, model)
     golden_submission_lines()
     ref_shim.uninstall()
+    gold_mapfree_records()
     print("golden fixtures written to", GOLD)
 
 

@@ -9,8 +9,7 @@ kinds) so that it can run on a box without the reference tree -- i.e. on the GPU
                        R, t = model(data) -> per item .detach().cpu().numpy(), data['inliers'][i].item(), NaN filter,
                        quaternion, 'name qw qx qy qz tx ty tz conf' lines zipped per scene
 
-The reference's own files run unmodified against the drop-in in tests/test_reference_callers.py (build container, no GPU);
-this module is the same traffic for tests/test_callers_gpu.py."""
+This module is that traffic for tests/test_callers_gpu.py."""
 import zipfile
 
 import numpy as np

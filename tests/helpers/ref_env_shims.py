@@ -1,7 +1,7 @@
 """Stand-ins for third-party modules the REFERENCE's callers import and this container lacks (cv2, yacs,
 pytorch_lightning, transforms3d, torchvision, pyrender, trimesh).  TEST INFRASTRUCTURE: used only by
-tests/helpers/run_reference_callers.py to execute the reference's own demo_inference.py / submission.py against the
-drop-in `lib` overlay.  None of them touches hot-path arithmetic."""
+tests/helpers/run_reference_dataset.py, which oracle/make_golden.py runs to record the reference's dataset outputs.
+None of them touches hot-path arithmetic."""
 import sys
 import types
 

@@ -1,6 +1,6 @@
 """Iterate the REFERENCE's MapFreeScene (lib/datasets/mapfree.py) over a dataset directory and dump what it yields.
-Subprocess of tests/test_mapfree_eval_cpu.py with PYTHONPATH = <reference checkout>; third-party modules this container
-lacks are stood in for by ref_env_shims (cv2 -> PIL, transforms3d: unused for test_scene=True)."""
+Subprocess of oracle/make_golden.py (tests/golden/mapfree_records.npz) with PYTHONPATH = <reference checkout>; third-party
+modules this container lacks are stood in for by ref_env_shims (cv2 -> PIL, transforms3d: unused for test_scene=True)."""
 import json
 import os
 import sys

@@ -153,3 +153,67 @@ def test_compact_line_at_eight_gpus_stays_small():
     assert len(txt) < bench.LINE_LIMIT
     line = json.loads(txt)
     assert line["n_gpus"] == 8 and line["per_rank_ms_per_step"] == {"min": 115.1, "max": 117.2} and "affinity" not in line["config"]
+
+
+def test_measure_times_exactly_the_requested_steps():
+    """--warmup W then --steps K forwards, no more: the last step's data dict is what measure() returns (and what
+    --dump-outputs writes).  --steps 0 is refused."""
+    import torch
+    calls = []
+
+    def model(data):
+        calls.append(len(calls))
+        data["R"] = torch.full((1, 3, 3), float(len(calls)))
+        return data["R"], data["R"]
+
+    data0 = {"image0": torch.zeros((1, 3, 8, 8))}
+    dt, last, poses = bench.measure(model, data0, argparse.Namespace(steps=3, warmup=2), False, 1, None)
+    assert len(calls) == 5 and float(last["R"][0, 0, 0]) == 5.0 and poses is None and dt > 0
+    assert bench.parse_args(["--steps", "7"]).steps == 7
+    with pytest.raises(SystemExit):
+        bench.parse_args(["--steps", "0"])
+
+
+def test_dump_outputs_budget_and_sample(tmp_path):
+    """Small outputs whole and exact (integers as float64), larger ones a seeded sample that is the same on every call,
+    inputs left out, all files together within the budget."""
+    import numpy as np
+    import torch
+    g = torch.Generator().manual_seed(5)
+    data = {"big": torch.randn((600, 700), generator=g), "wide": torch.randn((400, 300), generator=g, dtype=torch.float64),
+            "idx": torch.arange(10), "half": torch.randn((5, 7), generator=g).half(), "image0": torch.zeros(4), "shape": [3, 4]}
+    budget = 1 << 20
+    got = bench.dump_outputs(data, str(tmp_path / "a"), inputs={"image0"}, budget=budget)
+    bench.dump_outputs(data, str(tmp_path / "b"), inputs={"image0"}, budget=budget)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["big.npy", "half.npy", "idx.npy", "wide.npy"] and set(got) == {"big", "half", "idx", "wide"}
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= budget
+    for f in files:
+        assert open(tmp_path / "a" / f, "rb").read() == open(tmp_path / "b" / f, "rb").read(), f
+    load = {f[:-4]: np.load(tmp_path / "a" / f) for f in files}
+    assert load["idx"].dtype == np.float64 and np.array_equal(load["idx"], np.arange(10))
+    assert load["half"].dtype == np.float32 and np.array_equal(load["half"], data["half"].float().numpy())
+    for name, dtype in (("big", np.float32), ("wide", np.float64)):
+        n = got[name][1]
+        assert load[name].dtype == dtype and load[name].shape == (n,) and 0 < n < data[name].numel()
+        idx = torch.randint(data[name].numel(), (n,), generator=torch.Generator().manual_seed(0)).sort().values
+        assert np.array_equal(load[name], data[name].reshape(-1)[idx].numpy())
+
+
+def test_stub_dump_outputs_writes_the_last_step(tmp_path):
+    """--dump-outputs through the launcher: one process writes the poses of its batch; two ranks write the gathered poses of
+    the global batch (rank r's pairs at rows [r * B, (r + 1) * B)).  The stub's pose is a function of the seeded images."""
+    import numpy as np
+    import torch
+    for gpus in (1, 2):
+        d = tmp_path / str(gpus)
+        r = _run(["--gpus", str(gpus), "--dump-outputs", str(d)])
+        assert r.returncode == 0, r.stderr[-2000:]
+        assert sorted(os.listdir(d)) == ["R.npy", "inliers.npy", "t.npy"]
+        R = np.load(d / "R.npy")
+        assert R.dtype == np.float32 and R.shape == (3 * gpus, 3, 3)
+        for rank in range(gpus):
+            im = torch.rand((3, 3, 8, 8), generator=torch.Generator().manual_seed(1234 + 2 * rank))
+            m = im.reshape(3, -1).mean(1)
+            assert np.allclose(R[3 * rank:3 * rank + 3], (torch.eye(3).repeat(3, 1, 1) * m.view(3, 1, 1)).numpy(), rtol=0, atol=1e-7)
+            assert np.allclose(np.load(d / "inliers.npy")[3 * rank:3 * rank + 3], (10 * m).view(3, 1).numpy(), rtol=0, atol=1e-6)

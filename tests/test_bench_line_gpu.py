@@ -20,8 +20,10 @@ def test_last_stdout_line_is_small_and_complete(tmp_path):
     env = dict(os.environ)
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         env.pop(k, None)
+    dump = tmp_path / "outputs"
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--batch", "8", "--legs", "ref_split",
-                        "--detail", detail], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, env=env, timeout=900)
+                        "--detail", detail, "--dump-outputs", str(dump)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
+                       env=env, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     last = r.stdout.strip().splitlines()[-1]
     assert len(last) < 3072, len(last)
@@ -44,3 +46,12 @@ def test_last_stdout_line_is_small_and_complete(tmp_path):
     assert full["sustained"]["steps"] == 60 and len(full["cpu_baseline"]["runs_total_seconds"]) == 3
     assert full["cpu_baseline"]["threads_probe"]["measured_once"]["seconds_threads_256"] > 100   # (the all-cores probe is opt-in)
     assert "split" in full["legs"]["ref_split"]["heads_operands"]
+    # --dump-outputs: the timed forward's outputs, float32 / float64, within 64 MB (the [B, n, n] matrices sampled)
+    import numpy as np
+    files = os.listdir(dump)
+    assert sum(os.path.getsize(dump / f) for f in files) <= 64 * 10**6
+    out = {f[:-4]: np.load(dump / f) for f in files}
+    assert {"R", "t", "inliers", "kps0", "dsc0", "scr0", "depth_kp0", "scores", "final_scores"} <= set(out) and "image0" not in out
+    assert all(a.dtype in (np.float32, np.float64) for a in out.values())
+    assert out["R"].shape == (8, 3, 3) and out["t"].shape == (8, 1, 3) and np.isfinite(out["R"]).all()
+    assert out["final_scores"].ndim == 1 and 0 < out["final_scores"].size < 8 * 1938 * 1938

@@ -1,9 +1,7 @@
 """-m gpu: the call sequence of the reference's inference callers (demo_inference.py:79-138, submission.py:32-68 -- restated
 call for call in tests/helpers/caller_sequence.py, because the GPU box has no reference tree) driving the REAL HIP forward:
 build_model(cfg with attribute + key access, Lightning-style checkpoint without DINOv2 keys + the hub file beside it) ->
-.cuda() inside build_model -> model(data, return_inliers=True) with float64 intrinsics -> the keys the callers read back.
-(The reference's own, unmodified files run against the drop-in in tests/test_reference_callers.py, where the forward is the
-CPU oracle: there is no GPU in the build container.)"""
+.cuda() inside build_model -> model(data, return_inliers=True) with float64 intrinsics -> the keys the callers read back."""
 import os
 import sys
 import zipfile

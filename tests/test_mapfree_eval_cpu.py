@@ -1,18 +1,12 @@
 """Map-free evaluation harness, host side: it takes paths and skips cleanly; its scene parsing yields the reference
-dataset's pairs, names and intrinsics (compared with lib/datasets/mapfree.py run in a subprocess)."""
+dataset's pairs, names and intrinsics (compared with what lib/datasets/mapfree.py yields, stored in tests/golden)."""
 import json
 import os
-import subprocess
-import sys
 
 import numpy as np
-import pytest
 
 from mickey_amd import mapfree_eval as ME
 from tests.helpers import tiny_mapfree
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = os.environ.get("MICKEY_REFERENCE_ROOT", "/root/reference")
 
 
 def test_skips_cleanly_without_dataset_or_checkpoint(tmp_path, capsys):
@@ -52,32 +46,26 @@ def test_records_follow_the_dataset_layout(tmp_path):
     assert recs[0]["K_color0"].dtype == np.float32 and recs[0]["K_color0"].shape == (3, 3)
 
 
-@pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "lib", "datasets")), reason="reference tree not present")
-def test_records_match_the_reference_dataset(tmp_path):
+def test_records_match_the_reference_dataset(tmp_path, golden):
+    """Against what the reference's MapFreeScene yields over the same tiny dataset (tests/golden/mapfree_records.npz, written
+    by oracle/make_golden.py), at the stored size and at a larger model size."""
     import torch
     from mickey_amd.input_pipeline import correct_intrinsic_scale, decode_rgb
-    split_root = tiny_mapfree.make(str(tmp_path), "test", queries=12, size=(126, 168))
-    W, H = 126, 168          # same as stored: the reference's image tensors are then the decoded bytes / 255, no resampling
-    env = dict(os.environ, PYTHONPATH=REF + os.pathsep + ROOT)   # reference first: `lib.datasets` is its own
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "helpers", "run_reference_dataset.py"), split_root, str(W), str(H), "5"],
-                       stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, env=env, timeout=600)
-    assert r.returncode == 0, r.stdout[-3000:]
-    ref = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("RESULT ")][-1][7:])
+    ref = golden("mapfree_records")
+    W, H = (int(x) for x in ref["size"])   # model size == stored size: the reference's image tensors are the decoded bytes / 255
+    W2, H2 = (int(x) for x in ref["size2"])
+    tiny_mapfree.make(str(tmp_path), "test", queries=int(ref["queries"]), size=(W, H))
     recs = ME.dataset_records(str(tmp_path), "test", (W, H))
-    assert len(recs) == len(ref) == 2 * 3
-    for a, b in zip(recs, ref):
-        assert a["scene_id"] == b["scene_id"] and list(a["pair_names"]) == b["pair_names"]
-        assert np.array_equal(a["Kori_color0"], np.array(b["Kori_color0"], dtype=np.float32))
+    assert len(recs) == len(ref["scene_id"]) == 2 * 3
+    for i, a in enumerate(recs):
+        assert a["scene_id"] == ref["scene_id"][i] and list(a["pair_names"]) == list(ref["pair_names"][i])
+        assert np.array_equal(a["Kori_color0"], ref["Kori_color0"][i])
         img0 = decode_rgb(a["image0"]).astype(np.float64) / 255.0
-        assert list(img0.transpose(2, 0, 1).shape) == b["image0_shape"]
-        assert abs(float(np.float32(img0).astype(np.float64).sum()) - b["image0_sum"]) < 1e-2
+        assert list(img0.transpose(2, 0, 1).shape) == list(ref["image0_shape"][i])
+        assert abs(float(np.float32(img0).astype(np.float64).sum()) - float(ref["image0_sum"][i])) < 1e-2
     # intrinsics at a model resolution different from the stored one: the feeder's rescale == the reference's
-    r2 = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "helpers", "run_reference_dataset.py"), split_root, "270", "360", "5"],
-                        stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, env=env, timeout=600)
-    assert r2.returncode == 0, r2.stdout[-3000:]
-    ref2 = json.loads([ln for ln in r2.stdout.splitlines() if ln.startswith("RESULT ")][-1][7:])
-    for a, b in zip(recs, ref2):
-        K = correct_intrinsic_scale(torch.from_numpy(a["K_color0"]), 270 / 126, 360 / 168).numpy()
-        assert np.allclose(K, np.array(b["K_color0"], dtype=np.float32), rtol=0, atol=1e-4)
-        Ks, _, size = ME.read_intrinsics(os.path.dirname(os.path.dirname(a["image0"])), (270, 360))
-        assert np.allclose(Ks[a["pair_names"][0]], np.array(b["K_color0"], dtype=np.float32), rtol=0, atol=1e-4) and size == (126, 168)
+    for i, a in enumerate(recs):
+        K = correct_intrinsic_scale(torch.from_numpy(a["K_color0"]), W2 / W, H2 / H).numpy()
+        assert np.allclose(K, ref["K_color0_size2"][i], rtol=0, atol=1e-4)
+        Ks, _, size = ME.read_intrinsics(os.path.dirname(os.path.dirname(a["image0"])), (W2, H2))
+        assert np.allclose(Ks[a["pair_names"][0]], ref["K_color0_size2"][i], rtol=0, atol=1e-4) and size == (W, H)
