@@ -304,6 +304,25 @@ int mk_sinkhorn(const float* dsc0, const float* dsc1, const float* scr0, const f
                 float* scores, float* kp_scores, float* final_scores, float* work, int B, int C, int n0, int n1,
                 mk_stream_t stream);
 
+/* Keyframe mode of the three matchers: B pairs that share K <= B image-0 frames (Map-free val / test: every pair of a scene is
+ * its keyframe seq0/frame_00000 against one query frame, reference lib/datasets/mapfree.py:83-99).  Arguments as the entry
+ * point without _kf, except that dsc0 [K, C, n0] and scr0 [K, n0] hold the K keyframes and pair b reads row kf_index[b]:
+ *   kf_index  int32 [B] device map pair -> keyframe, or NULL = the identity (then K must equal B: the call IS the one without _kf).
+ *   PRECONDITION: 0 <= kf_index[b] < K for every b; the caller validates the map on the host (mickey_amd.ops.check_keyframe_index).
+ *             A kernel never dereferences an entry outside [0, K): the workgroups of such a pair return without reading, and its
+ *             outputs are left unwritten.
+ * Work sizes: the same *_work_floats(B, n0, n1) as the call without _kf (K <= B: operand 0 only gets smaller).
+ * mk_dual_softmax_split_kf makes the split planes of each keyframe ONCE (K, not B, plane sets). */
+int mk_dual_softmax_kf(const float* dsc0, const float* dsc1, const float* scr0, const float* scr1, float inv_temperature,
+                       int use_dustbin, float dustbin, float* scores, float* kp_scores, float* final_scores, float* work, int B,
+                       int C, int n0, int n1, const int* kf_index, int K, mk_stream_t stream);
+int mk_dual_softmax_split_kf(const float* dsc0, const float* dsc1, const float* scr0, const float* scr1, float inv_temperature,
+                             int use_dustbin, float dustbin, float* scores, float* kp_scores, float* final_scores, float* work,
+                             int B, int C, int n0, int n1, const int* kf_index, int K, mk_stream_t stream);
+int mk_sinkhorn_kf(const float* dsc0, const float* dsc1, const float* scr0, const float* scr1, float alpha, int iters,
+                   float* scores, float* kp_scores, float* final_scores, float* work, int B, int C, int n0, int n1,
+                   const int* kf_index, int K, mk_stream_t stream);
+
 /* featureMatcher.get_matches_list (feature_matcher.py:19-46), batched: mutual nearest neighbours on
  * scores[b, :n0-1, :n1-1], sorted by score descending.  matches int32 [B, n0, 2] (row i, col j),
  * count int32 [B].  work: 2*B*(n0+n1) ints. */
@@ -358,6 +377,15 @@ int mk_counter_add(unsigned long long* counter, unsigned long long inc, mk_strea
 int mk_gather_backproject(const int* idx, const float* final_scores, const float* kps0, const float* depth0,
                           const float* kps1, const float* depth1, const float* K0, const float* K1, float* X, float* Y,
                           float* wts, float* corr, int B, int rows_per_pair, int k, int n0, int n1, mk_stream_t stream);
+
+/* Keyframe mode of mk_gather_backproject (the pairs of a Map-free scene share its keyframe, reference
+ * lib/datasets/mapfree.py:83-99): kps0 [K, 2, n0] and depth0 [K, n0] hold the K <= B keyframes, pair b reads row kf_index[b];
+ * K0 stays per pair [B, 3, 3].  kf_index: int32 [B] device map, NULL = the identity (K == B).  PRECONDITION and
+ * out-of-range behaviour as mk_dual_softmax_kf. */
+int mk_gather_backproject_kf(const int* idx, const float* final_scores, const float* kps0, const float* depth0,
+                             const float* kps1, const float* depth1, const float* K0, const float* K1, float* X, float* Y,
+                             float* wts, float* corr, int B, int rows_per_pair, int k, int n0, int n1, const int* kf_index,
+                             int K, mk_stream_t stream);
 
 /* Backward of mk_gather_backproject w.r.t. keypoints and depths (training: loss_class.py:139-146 + training_utils.py:7-22 under
  * autograd; intrinsics and scores get no gradient).  gX, gY [B*rows_per_pair, k, 3] = dL/dX, dL/dY; corr as written by the forward;

@@ -54,12 +54,16 @@ SIGNATURES = {
     "mk_dual_softmax_split": ("i", "ppppfifppppiiiip"),
     "mk_sinkhorn_work_floats": ("l", "iii"),
     "mk_sinkhorn": ("i", "ppppfippppiiiip"),
+    "mk_dual_softmax_kf": ("i", "ppppfifppppiiiipip"),
+    "mk_dual_softmax_split_kf": ("i", "ppppfifppppiiiipip"),
+    "mk_sinkhorn_kf": ("i", "ppppfippppiiiipip"),
     "mk_mutual_nn": ("i", "ppppiiip"),
     "mk_exprace_topk_work_bytes": ("l", "iiil"),
     "mk_exprace_topk_state_bytes": ("l", "ii"),
     "mk_exprace_topk": ("i", "ppuupppppiiliip"),
     "mk_counter_add": ("i", "pup"),
     "mk_gather_backproject": ("i", "ppppppppppppiiiiip"),
+    "mk_gather_backproject_kf": ("i", "ppppppppppppiiiiipip"),
     "mk_gather_backproject_bwd": ("i", "ppppppppppiiiiip"),
     "mk_ransac_hypotheses": ("i", "pppppuupfppppiiilp"),
     "mk_refine_pose": ("i", "pppppfiipppppppiiiip"),

@@ -37,6 +37,20 @@ void mk_set_error(const char* fmt, ...);
 
 namespace mk {
 
+// Keyframe mode (mickey_hip.h: the *_kf entry points): the row of operand 0 that pair b reads, map[b].  b comes from blockIdx, so
+// the entry is block-uniform: it is loaded once per workgroup and passed through readfirstlane, which lets hipcc prove every
+// pointer / buffer descriptor built from it wave-uniform (no readfirstlane waterfall loop around the memory ops).  KF = false is the
+// identity and compiles to nothing.  Returns false for an entry outside [0, K): the workgroup then returns without reading.
+template <bool KF>
+__device__ __forceinline__ bool kf_row(const int* __restrict__ map, int K, int b, int& row) {
+  if (!KF) {
+    row = b;
+    return true;
+  }
+  row = __builtin_amdgcn_readfirstlane(map[b]);
+  return (unsigned)row < (unsigned)K;
+}
+
 // Split-operand planes (x * scale = hi + lo in fp16) saturate at fp16's largest finite value; a NaN stays a NaN (both planes), so
 // that a non-finite head activation reaches the outputs and the callers' finite checks.  flag: the per-call watcher word of the
 // plane-writing entry points (mickey_hip.h: sat_flag; null = nobody watches: no per-element work) gets bit 0 set by any kernel

@@ -138,14 +138,16 @@ __device__ __forceinline__ f32x16 corr_regs(const float (&a)[CMAX / 2], const fl
 //     correlation (the fp32 matrix pipe is the bound of this stage: 64 MFMAs x 64 cycles per 32 x 32 tile).
 // amdgpu_waves_per_eu(2, 2): without it the scheduler chases occupancy, keeps ONE operand register and emits
 // load -> s_waitcnt vmcnt(0) -> MFMA 64 times per tile (64 serial memory round trips, measured 32 us per tile)
-template <bool FULLC>
+// KF (keyframe mode): dsc0 holds K keyframes, pair b reads row kf[b] (kf_row); partials and vbuf stay per pair
+template <bool FULLC, bool KF>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void lse_partial_kernel(const float* __restrict__ dsc0, const float* __restrict__ dsc1,
                                                           float scale2, float* __restrict__ partr, float* __restrict__ partc,
                                                           float* __restrict__ vbuf, int C, int n0, int n1, int nrb, int gx,
-                                                          int nunits) {
-  int bx, by, b;
+                                                          int nunits, const int* __restrict__ kf, int K) {
+  int bx, by, b, b0;
   if (!decode_unit_grid(gx, NCHUNK, nunits, bx, by, b)) return;
-  const float* dA = dsc0 + (long long)b * C * n0;
+  if (!kf_row<KF>(kf, K, b, b0)) return;
+  const float* dA = dsc0 + (long long)b0 * C * n0;
   const float* dB = dsc1 + (long long)b * C * n1;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int l31 = lane & 31, hi = lane >> 5;
@@ -245,16 +247,19 @@ __global__ __launch_bounds__(256) void lse_final_kernel(const float* __restrict_
 
 // pass 2, element-wise.  grid (column blocks of 256*VEC, n0, B): scores = softmax_rows * softmax_cols =
 // 2^((v2 - lc2) + (v2 - lr2)), kp = scr0 (x) scr1, final = scores * kp.  `scores` or `fin` may alias vbuf (in place).
-template <int VEC>
+// KF: scr0 holds K keyframes, pair b reads row kf[b]
+template <int VEC, bool KF>
 __global__ __launch_bounds__(256) void dual_softmax_apply_kernel(const float* vbuf, const float* __restrict__ scr0,
                                                                  const float* __restrict__ scr1, const float* __restrict__ lse2,
                                                                  float* scores, float* __restrict__ kp, float* fin, int n0, int n1,
-                                                                 int nmax) {
+                                                                 int nmax, const int* __restrict__ kf, int K) {
   const int i = blockIdx.y, b = blockIdx.z;
+  int b0;
+  if (!kf_row<KF>(kf, K, b, b0)) return;
   const int j = (blockIdx.x * 256 + threadIdx.x) * VEC;
   if (j >= n1) return;
   const float lr = lse2[((long long)b * 2 + 0) * nmax + i];
-  const float s0 = scr0 ? scr0[(long long)b * n0 + i] : 0.f;
+  const float s0 = scr0 ? scr0[(long long)b0 * n0 + i] : 0.f;
   const long long o = ((long long)b * n0 + i) * n1 + j;
   typedef float VT __attribute__((ext_vector_type(VEC)));
   const VT v = __builtin_nontemporal_load((const VT*)(vbuf + o));   // read once, overwritten in place
@@ -343,17 +348,20 @@ __device__ __forceinline__ f32x16 corr_split(const SplitOperand& a, const SplitO
 
 // pass 1.  grid: decode_unit_grid(gx = row blocks / 4, NCHUNK_S, B); one wave per 32 rows and one chunk of column tiles.
 // partr[((b*NCHUNK_S + chunk)*n0 + row)] = (0, sum_j 2^v2), partc[((b*nrb + rb)*n1 + j)] = (0, sum over the block's rows)
+// KF: P0 holds the planes of K keyframes, pair b reads those of kf[b]
+template <bool KF>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void lse_split_kernel(
     const uint4* __restrict__ P0, const uint4* __restrict__ P1, float scale2, float* __restrict__ partr, float* __restrict__ partc,
-    int n0, int n1, int nrb, int ntb, int gx, int nunits) {
-  int bx, by, b;
+    int n0, int n1, int nrb, int ntb, int gx, int nunits, const int* __restrict__ kf, int K) {
+  int bx, by, b, b0;
   if (!decode_unit_grid(gx, NCHUNK_S, nunits, bx, by, b)) return;
+  if (!kf_row<KF>(kf, K, b, b0)) return;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int l31 = lane & 31, hi = lane >> 5;
   const int rb = bx * 4 + wave, i0 = rb * RT;
   if (rb >= nrb) return;
   SplitOperand a, bq;
-  a.load(P0 + ((long long)b * nrb + rb) * SP_BLK_U4, lane);
+  a.load(P0 + ((long long)b0 * nrb + rb) * SP_BLK_U4, lane);
   const int per = (ntb + NCHUNK_S - 1) / NCHUNK_S;
   const int jt0 = by * per, jt1 = min(ntb, jt0 + per);
   float rs[16];
@@ -419,22 +427,25 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 // half of this kernel's time is the latency of re-computing the correlation (three dependent L2 round trips per wave for 48
 // MFMAs), which eight independent waves per CU overlap with each other's stores and four barrier-coupled ones do not.
 // scores = 2^((v2 - lc2) + (v2 - lr2)), kp = scr0 (x) scr1, final = scores kp.
-template <int VEC>   // floats per lane of an output store: 4 when the output rows are 16-byte aligned (n1 % 4 == 0), 2 for even n1
+template <int VEC,   // floats per lane of an output store: 4 when the output rows are 16-byte aligned (n1 % 4 == 0), 2 for even n1
                      // (n1 = 1938, the Map-free grid), else 1
+          bool KF>   // keyframe mode: P0 / scr0 hold K keyframes, pair b reads kf[b]
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void dual_softmax_split_apply_kernel(
     const uint4* __restrict__ P0, const uint4* __restrict__ P1, float scale2, const float* __restrict__ scr0,
     const float* __restrict__ scr1, const float* __restrict__ lse2, float* __restrict__ scores, float* __restrict__ kp,
-    float* __restrict__ fin, int n0, int n1, int nmax, int nrb, int ntb, int gx, int nunits, int nchunk) {
+    float* __restrict__ fin, int n0, int n1, int nmax, int nrb, int ntb, int gx, int nunits, int nchunk, const int* __restrict__ kf,
+    int K) {
   __shared__ __attribute__((aligned(16))) float stage[4][RT * 64];
-  int bx, by, b;
+  int bx, by, b, b0;
   if (!decode_unit_grid<true>(gx, nchunk, nunits, bx, by, b)) return;
+  if (!kf_row<KF>(kf, K, b, b0)) return;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int l31 = lane & 31, hi = lane >> 5;
   const int rb = bx * 4 + wave, i0 = rb * RT;
   if (rb >= nrb) return;
   float* st = stage[wave];
   SplitOperand a, bq;
-  a.load(P0 + ((long long)b * nrb + rb) * SP_BLK_U4, lane);
+  a.load(P0 + ((long long)b0 * nrb + rb) * SP_BLK_U4, lane);
   const int per = (ntb + nchunk - 1) / nchunk;
   const int jt0 = by * per, jt1 = min(ntb, jt0 + per);
   float lr[16], s0[16];
@@ -443,7 +454,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     const int i = i0 + (r & 3) + 8 * (r >> 2) + 4 * hi;
     const int ic = i < n0 ? i : n0 - 1;
     lr[r] = lse2[((long long)b * 2 + 0) * nmax + ic];
-    s0[r] = scr0 ? scr0[(long long)b * n0 + ic] : 0.f;
+    s0[r] = scr0 ? scr0[(long long)b0 * n0 + ic] : 0.f;
   }
   const uint4* pb = P1 + (long long)b * ntb * SP_BLK_U4;
   typedef float VT __attribute__((ext_vector_type(VEC)));
@@ -501,15 +512,19 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 constexpr int SK_RCH = 256;   // rows per chunk of the column pass
 
 // Z2[(n0+1) x ldz] = couplings * log2(e) (S / sqrt(C), alpha on the last row / column / corner, -1e30 in the row pad)
+// KF: dsc0 holds K keyframes, pair b reads row kf[b]
+template <bool KF>
 __global__ __launch_bounds__(256) void couplings_kernel(const float* __restrict__ dsc0, const float* __restrict__ dsc1,
                                                         float scale2, float alpha2, float* __restrict__ Z, int C, int n0,
-                                                        int n1, int ldz) {
+                                                        int n1, int ldz, const int* __restrict__ kf, int K) {
   __shared__ __attribute__((aligned(16))) float sA[CMAX * MT];
   __shared__ __attribute__((aligned(16))) float sB[CMAX * MT];
   const int b = blockIdx.z, i0 = blockIdx.y * MT, j0 = blockIdx.x * MT;
+  int b0;
+  if (!kf_row<KF>(kf, K, b, b0)) return;   // (the whole workgroup: before the barrier)
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, wi = wave >> 1, wj = wave & 1;
   const int l31 = lane & 31, hi = lane >> 5;
-  stage_desc(sA, dsc0 + (long long)b * C * n0, C, n0, i0);
+  stage_desc(sA, dsc0 + (long long)b0 * C * n0, C, n0, i0);
   stage_desc(sB, dsc1 + (long long)b * C * n1, C, n1, j0);
   __syncthreads();
   const f32x16 acc = corr_tile(sA, sB, C, wi, wj, lane);
@@ -621,12 +636,17 @@ __global__ __launch_bounds__(256) void sink_col_fin_kernel(const float2* __restr
   v[(long long)b * ldz + j] = j > n1 ? 0.f : (j == n1 ? last2 : norm2) - (m + __builtin_amdgcn_logf(s));
 }
 
+// KF: scr0 holds K keyframes, pair b reads row kf[b]
+template <bool KF>
 __global__ __launch_bounds__(256) void sink_final_kernel(const float* __restrict__ Z, const float* __restrict__ u,
                                                          const float* __restrict__ v, float norm2,
                                                          const float* __restrict__ scr0, const float* __restrict__ scr1,
                                                          float* __restrict__ out, float* __restrict__ kp,
-                                                         float* __restrict__ fin, int n0, int n1, int ldz, int ldu) {
+                                                         float* __restrict__ fin, int n0, int n1, int ldz, int ldu,
+                                                         const int* __restrict__ kf, int K) {
   const int b = blockIdx.z, i = blockIdx.y;
+  int b0;
+  if (!kf_row<KF>(kf, K, b, b0)) return;
   const int j = blockIdx.x * 256 + threadIdx.x;
   if (j >= n1) return;
   const float z = Z[((long long)b * (n0 + 1) + i) * ldz + j];
@@ -634,7 +654,7 @@ __global__ __launch_bounds__(256) void sink_final_kernel(const float* __restrict
   const long long o = ((long long)b * n0 + i) * n1 + j;
   if (out) out[o] = pr;
   if (scr0) {
-    const float kk = scr0[(long long)b * n0 + i] * scr1[(long long)b * n1 + j];
+    const float kk = scr0[(long long)b0 * n0 + i] * scr1[(long long)b * n1 + j];
     if (kp) kp[o] = kk;
     if (fin) fin[o] = pr * kk;
   }
@@ -763,13 +783,15 @@ long long mk_dual_softmax_work_floats(int B, int n0, int n1, int own_copy) {
          (own_copy ? (long long)B * n0 * n1 : 0);
 }
 
-int mk_dual_softmax(const float* dsc0, const float* dsc1, const float* scr0, const float* scr1, float inv_temperature,
-                    int use_dustbin, float dustbin, float* scores, float* kp_scores, float* final_scores, float* work, int B,
-                    int C, int n0, int n1, mk_stream_t stream) {
-  MK_CHECK_ARG(dsc0 && dsc1 && work, "mk_dual_softmax: null pointer");
+}  // extern "C"
+
+// the exact-fp32 dual softmax; KF: keyframe mode (operand 0 read through kf, mickey_hip.h: mk_dual_softmax_kf)
+template <bool KF>
+static int dual_softmax_impl(const float* dsc0, const float* dsc1, const float* scr0, const float* scr1, float inv_temperature,
+                             int use_dustbin, float dustbin, float* scores, float* kp_scores, float* final_scores, float* work, int B,
+                             int C, int n0, int n1, const int* kf, int K, hipStream_t st) {
   MK_CHECK_ARG(B > 0 && n0 > 0 && n1 > 0 && C > 0 && C <= CMAX && C % 2 == 0, "mk_dual_softmax: need 0 < C <= %d, C even", CMAX);
   MK_CHECK_ARG((scr0 && scr1) || (!kp_scores && !final_scores), "mk_dual_softmax: kp/final scores need scr0 and scr1");
-  hipStream_t st = (hipStream_t)stream;
   const int nmax = n0 > n1 ? n0 : n1, nrb = (n0 + RT - 1) / RT;
   const float LOG2E = 1.4426950408889634f;
   const float scale2 = inv_temperature * LOG2E;
@@ -782,9 +804,11 @@ int mk_dual_softmax(const float* dsc0, const float* dsc1, const float* scr0, con
   const int gx1 = (n0 + 4 * RT - 1) / (4 * RT);
   const dim3 g1((unsigned)gx1 * NCHUNK * ((B + 7) / 8 * 8));   // see decode_unit_grid
   if (C == CMAX)
-    hipLaunchKernelGGL(lse_partial_kernel<true>, g1, dim3(256), 0, st, dsc0, dsc1, scale2, partr, partc, vbuf, C, n0, n1, nrb, gx1, B);
+    hipLaunchKernelGGL((lse_partial_kernel<true, KF>), g1, dim3(256), 0, st, dsc0, dsc1, scale2, partr, partc, vbuf, C, n0, n1, nrb, gx1, B,
+                       kf, K);
   else
-    hipLaunchKernelGGL(lse_partial_kernel<false>, g1, dim3(256), 0, st, dsc0, dsc1, scale2, partr, partc, vbuf, C, n0, n1, nrb, gx1, B);
+    hipLaunchKernelGGL((lse_partial_kernel<false, KF>), g1, dim3(256), 0, st, dsc0, dsc1, scale2, partr, partc, vbuf, C, n0, n1, nrb, gx1, B,
+                       kf, K);
   MK_CHECK_LAUNCH();
   hipLaunchKernelGGL(lse_final_kernel, dim3((nmax + 255) / 256, 2, B), dim3(256), 0, st, partr, partc, lse2, use_dustbin,
                      dustbin * LOG2E, n0, n1, nmax, nrb, NCHUNK);
@@ -794,14 +818,35 @@ int mk_dual_softmax(const float* dsc0, const float* dsc1, const float* scr0, con
     const bool v2 = (n1 % 2 == 0) && ((((uintptr_t)vbuf | (uintptr_t)scores | (uintptr_t)kp_scores | (uintptr_t)final_scores |
                                         (uintptr_t)scr1 | (uintptr_t)lse2) & 7) == 0) && (nmax % 2 == 0);
     if (v2)
-      hipLaunchKernelGGL(dual_softmax_apply_kernel<2>, dim3((n1 / 2 + 255) / 256, n0, B), dim3(256), 0, st, vbuf, scr0, scr1, lse2,
-                         scores, kp_scores, final_scores, n0, n1, nmax);
+      hipLaunchKernelGGL((dual_softmax_apply_kernel<2, KF>), dim3((n1 / 2 + 255) / 256, n0, B), dim3(256), 0, st, vbuf, scr0, scr1, lse2,
+                         scores, kp_scores, final_scores, n0, n1, nmax, kf, K);
     else
-      hipLaunchKernelGGL(dual_softmax_apply_kernel<1>, dim3((n1 + 255) / 256, n0, B), dim3(256), 0, st, vbuf, scr0, scr1, lse2, scores,
-                         kp_scores, final_scores, n0, n1, nmax);
+      hipLaunchKernelGGL((dual_softmax_apply_kernel<1, KF>), dim3((n1 + 255) / 256, n0, B), dim3(256), 0, st, vbuf, scr0, scr1, lse2, scores,
+                         kp_scores, final_scores, n0, n1, nmax, kf, K);
     MK_CHECK_LAUNCH();
   }
   return MK_OK;
+}
+
+extern "C" {
+
+int mk_dual_softmax(const float* dsc0, const float* dsc1, const float* scr0, const float* scr1, float inv_temperature,
+                    int use_dustbin, float dustbin, float* scores, float* kp_scores, float* final_scores, float* work, int B,
+                    int C, int n0, int n1, mk_stream_t stream) {
+  return mk_dual_softmax_kf(dsc0, dsc1, scr0, scr1, inv_temperature, use_dustbin, dustbin, scores, kp_scores, final_scores, work, B, C,
+                            n0, n1, nullptr, B, stream);
+}
+
+int mk_dual_softmax_kf(const float* dsc0, const float* dsc1, const float* scr0, const float* scr1, float inv_temperature,
+                       int use_dustbin, float dustbin, float* scores, float* kp_scores, float* final_scores, float* work, int B,
+                       int C, int n0, int n1, const int* kf_index, int K, mk_stream_t stream) {
+  MK_CHECK_ARG(dsc0 && dsc1 && work, "mk_dual_softmax: null pointer");
+  MK_CHECK_ARG(kf_index ? (K > 0 && K <= B) : K == B, "mk_dual_softmax_kf: need 0 < K <= B with a keyframe map, K == B without");
+  if (kf_index)
+    return dual_softmax_impl<true>(dsc0, dsc1, scr0, scr1, inv_temperature, use_dustbin, dustbin, scores, kp_scores, final_scores, work,
+                                   B, C, n0, n1, kf_index, K, (hipStream_t)stream);
+  return dual_softmax_impl<false>(dsc0, dsc1, scr0, scr1, inv_temperature, use_dustbin, dustbin, scores, kp_scores, final_scores, work,
+                                  B, C, n0, n1, nullptr, B, (hipStream_t)stream);
 }
 
 long long mk_dual_softmax_split_work_floats(int B, int n0, int n1) {
@@ -811,10 +856,14 @@ long long mk_dual_softmax_split_work_floats(int B, int n0, int n1) {
          (long long)B * 2 * nmax + 8;
 }
 
-int mk_dual_softmax_split(const float* dsc0, const float* dsc1, const float* scr0, const float* scr1, float inv_temperature,
-                          int use_dustbin, float dustbin, float* scores, float* kp_scores, float* final_scores, float* work,
-                          int B, int C, int n0, int n1, mk_stream_t stream) {
-  MK_CHECK_ARG(dsc0 && dsc1 && work, "mk_dual_softmax_split: null pointer");
+}  // extern "C"
+
+// the split-fp16 dual softmax; KF: keyframe mode (mickey_hip.h: mk_dual_softmax_split_kf): the planes of operand 0 are made for the
+// K keyframes only (rows [0, K) of P0's B-pair region) and the passes address them through kf
+template <bool KF>
+static int dual_softmax_split_impl(const float* dsc0, const float* dsc1, const float* scr0, const float* scr1, float inv_temperature,
+                                   int use_dustbin, float dustbin, float* scores, float* kp_scores, float* final_scores, float* work,
+                                   int B, int C, int n0, int n1, const int* kf, int K, hipStream_t st) {
   MK_CHECK_ARG(B > 0 && n0 > 0 && n1 > 0 && C == 16 * SP_KS, "mk_dual_softmax_split: C must be %d (use mk_dual_softmax otherwise)", 16 * SP_KS);
   MK_CHECK_ARG((scr0 && scr1) || (!kp_scores && !final_scores), "mk_dual_softmax_split: kp/final scores need scr0 and scr1");
   MK_CHECK_ARG(((uintptr_t)work & 15) == 0, "mk_dual_softmax_split: work must be 16-byte aligned");
@@ -822,20 +871,19 @@ int mk_dual_softmax_split(const float* dsc0, const float* dsc1, const float* scr
   // unit-norm descriptors: |v2| <= inv_T log2(e); the maximum-free sums of pass 1 need 2^v2 and n 2^v2 inside fp32
   MK_CHECK_ARG(inv_temperature > 0.f && inv_temperature * LOG2E <= 100.f,
                "mk_dual_softmax_split: temperature %g too small for the maximum-free sums (use mk_dual_softmax)", 1.0 / inv_temperature);
-  hipStream_t st = (hipStream_t)stream;
   const int nmax = n0 > n1 ? n0 : n1, nrb = (n0 + RT - 1) / RT, ntb = (n1 + RT - 1) / RT;
   uint4* P0 = (uint4*)work;
   uint4* P1 = P0 + (long long)B * nrb * SP_BLK_U4;
   float* partr = (float*)(P1 + (long long)B * ntb * SP_BLK_U4);
   float* partc = partr + (long long)B * NCHUNK_S * n0 * 2;
   float* lse2 = partc + (long long)B * nrb * n1 * 2;
-  hipLaunchKernelGGL(dsc_split_kernel, dim3(nrb, B), dim3(512), 0, st, dsc0, P0, n0, nrb);
+  hipLaunchKernelGGL(dsc_split_kernel, dim3(nrb, K), dim3(512), 0, st, dsc0, P0, n0, nrb);
   hipLaunchKernelGGL(dsc_split_kernel, dim3(ntb, B), dim3(512), 0, st, dsc1, P1, n1, ntb);
   MK_CHECK_LAUNCH();
   const float scale2 = inv_temperature * LOG2E / (SP_SCALE * SP_SCALE);
   const int gx = (nrb + 3) / 4;
   const dim3 g((unsigned)gx * NCHUNK_S * ((B + 7) / 8 * 8));   // see decode_unit_grid
-  hipLaunchKernelGGL(lse_split_kernel, g, dim3(256), 0, st, P0, P1, scale2, partr, partc, n0, n1, nrb, ntb, gx, B);
+  hipLaunchKernelGGL(lse_split_kernel<KF>, g, dim3(256), 0, st, P0, P1, scale2, partr, partc, n0, n1, nrb, ntb, gx, B, kf, K);
   MK_CHECK_LAUNCH();
   hipLaunchKernelGGL(lse_final_kernel, dim3((nmax + 255) / 256, 2, B), dim3(256), 0, st, partr, partc, lse2, use_dustbin,
                      dustbin * LOG2E, n0, n1, nmax, nrb, NCHUNK_S);
@@ -847,17 +895,38 @@ int mk_dual_softmax_split(const float* dsc0, const float* dsc1, const float* scr
     const dim3 g2((unsigned)gx * nchunk2 * ((B + 7) / 8 * 8));
     const bool a16 = ((((uintptr_t)scores | (uintptr_t)kp_scores | (uintptr_t)final_scores) & 15) == 0);
     if ((n1 & 3) == 0 && a16)
-      hipLaunchKernelGGL(dual_softmax_split_apply_kernel<4>, g2, dim3(256), 0, st, P0, P1, scale2, scr0, scr1, lse2, scores, kp_scores,
-                         final_scores, n0, n1, nmax, nrb, ntb, gx, B, nchunk2);
+      hipLaunchKernelGGL((dual_softmax_split_apply_kernel<4, KF>), g2, dim3(256), 0, st, P0, P1, scale2, scr0, scr1, lse2, scores, kp_scores,
+                         final_scores, n0, n1, nmax, nrb, ntb, gx, B, nchunk2, kf, K);
     else if ((n1 & 1) == 0 && ((((uintptr_t)scores | (uintptr_t)kp_scores | (uintptr_t)final_scores) & 7) == 0))
-      hipLaunchKernelGGL(dual_softmax_split_apply_kernel<2>, g2, dim3(256), 0, st, P0, P1, scale2, scr0, scr1, lse2, scores, kp_scores,
-                         final_scores, n0, n1, nmax, nrb, ntb, gx, B, nchunk2);
+      hipLaunchKernelGGL((dual_softmax_split_apply_kernel<2, KF>), g2, dim3(256), 0, st, P0, P1, scale2, scr0, scr1, lse2, scores, kp_scores,
+                         final_scores, n0, n1, nmax, nrb, ntb, gx, B, nchunk2, kf, K);
     else
-      hipLaunchKernelGGL(dual_softmax_split_apply_kernel<1>, g2, dim3(256), 0, st, P0, P1, scale2, scr0, scr1, lse2, scores, kp_scores,
-                         final_scores, n0, n1, nmax, nrb, ntb, gx, B, nchunk2);
+      hipLaunchKernelGGL((dual_softmax_split_apply_kernel<1, KF>), g2, dim3(256), 0, st, P0, P1, scale2, scr0, scr1, lse2, scores, kp_scores,
+                         final_scores, n0, n1, nmax, nrb, ntb, gx, B, nchunk2, kf, K);
     MK_CHECK_LAUNCH();
   }
   return MK_OK;
+}
+
+extern "C" {
+
+int mk_dual_softmax_split(const float* dsc0, const float* dsc1, const float* scr0, const float* scr1, float inv_temperature,
+                          int use_dustbin, float dustbin, float* scores, float* kp_scores, float* final_scores, float* work,
+                          int B, int C, int n0, int n1, mk_stream_t stream) {
+  return mk_dual_softmax_split_kf(dsc0, dsc1, scr0, scr1, inv_temperature, use_dustbin, dustbin, scores, kp_scores, final_scores, work,
+                                  B, C, n0, n1, nullptr, B, stream);
+}
+
+int mk_dual_softmax_split_kf(const float* dsc0, const float* dsc1, const float* scr0, const float* scr1, float inv_temperature,
+                             int use_dustbin, float dustbin, float* scores, float* kp_scores, float* final_scores, float* work,
+                             int B, int C, int n0, int n1, const int* kf_index, int K, mk_stream_t stream) {
+  MK_CHECK_ARG(dsc0 && dsc1 && work, "mk_dual_softmax_split: null pointer");
+  MK_CHECK_ARG(kf_index ? (K > 0 && K <= B) : K == B, "mk_dual_softmax_split_kf: need 0 < K <= B with a keyframe map, K == B without");
+  if (kf_index)
+    return dual_softmax_split_impl<true>(dsc0, dsc1, scr0, scr1, inv_temperature, use_dustbin, dustbin, scores, kp_scores, final_scores,
+                                         work, B, C, n0, n1, kf_index, K, (hipStream_t)stream);
+  return dual_softmax_split_impl<false>(dsc0, dsc1, scr0, scr1, inv_temperature, use_dustbin, dustbin, scores, kp_scores, final_scores,
+                                        work, B, C, n0, n1, nullptr, B, (hipStream_t)stream);
 }
 
 static inline int sk_ldz(int n1) { return (n1 + 1 + 3) & ~3; }
@@ -870,13 +939,16 @@ long long mk_sinkhorn_work_floats(int B, int n0, int n1) {
   return (long long)B * ((long long)(n0 + 1) * ldz + sk_ldu(n0) + ldz + 2LL * sk_nrc(n0) * ldz);
 }
 
-int mk_sinkhorn(const float* dsc0, const float* dsc1, const float* scr0, const float* scr1, float alpha, int iters, float* scores,
-                float* kp_scores, float* final_scores, float* work, int B, int C, int n0, int n1, mk_stream_t stream) {
-  MK_CHECK_ARG(dsc0 && dsc1 && work && (scores || final_scores), "mk_sinkhorn: null pointer");
+}  // extern "C"
+
+// KF: keyframe mode (mickey_hip.h: mk_sinkhorn_kf): operand 0 (dsc0, scr0) read through kf; a pair group passes its slice of the map
+template <bool KF>
+static int sinkhorn_impl(const float* dsc0, const float* dsc1, const float* scr0, const float* scr1, float alpha, int iters, float* scores,
+                         float* kp_scores, float* final_scores, float* work, int B, int C, int n0, int n1, const int* kf, int K,
+                         hipStream_t st) {
   MK_CHECK_ARG((scr0 && scr1) || (!kp_scores && !final_scores), "mk_sinkhorn: kp/final scores need scr0 and scr1");
   MK_CHECK_ARG(B > 0 && n0 > 0 && n1 > 0 && C > 0 && C <= CMAX && C % 2 == 0 && iters >= 0, "mk_sinkhorn: bad args");
   MK_CHECK_ARG(((uintptr_t)work & 15) == 0, "mk_sinkhorn: work must be 16-byte aligned");
-  hipStream_t st = (hipStream_t)stream;
   const int ldz = sk_ldz(n1), ldu = sk_ldu(n0), nrc = sk_nrc(n0);
   float* Z = work;
   float* u = Z + (long long)B * (n0 + 1) * ldz;
@@ -898,14 +970,15 @@ int mk_sinkhorn(const float* dsc0, const float* dsc1, const float* scr0, const f
   const bool nt = g_sk_group <= 0 || (long long)group * zbytes > (240LL << 20);
   for (int b0 = 0; b0 < B; b0 += group) {
     const int nb = group < B - b0 ? group : B - b0;
-    const float* d0 = dsc0 + (long long)b0 * C * n0;
+    const float* d0 = KF ? dsc0 : dsc0 + (long long)b0 * C * n0;   // (keyframe mode: the group's map slice selects the rows)
+    const int* kg = KF ? kf + b0 : nullptr;
     const float* d1 = dsc1 + (long long)b0 * C * n1;
     float* Zg = Z + (long long)b0 * (n0 + 1) * ldz;
     float* ug = u + (long long)b0 * ldu;
     float* vg = v + (long long)b0 * ldz;
     float2* pg = part + (long long)b0 * nrc * ldz;
-    hipLaunchKernelGGL(couplings_kernel, dim3((ldz + MT - 1) / MT, (n0 + 1 + MT - 1) / MT, nb), dim3(256), 0, st, d0, d1,
-                       LOG2E / sqrtf((float)C), alpha * LOG2E, Zg, C, n0, n1, ldz);
+    hipLaunchKernelGGL(couplings_kernel<KF>, dim3((ldz + MT - 1) / MT, (n0 + 1 + MT - 1) / MT, nb), dim3(256), 0, st, d0, d1,
+                       LOG2E / sqrtf((float)C), alpha * LOG2E, Zg, C, n0, n1, ldz, kg, K);
     MK_CHECK_LAUNCH();
     hipLaunchKernelGGL(fill_kernel, dim3((unsigned)(((long long)nb * ldu + 255) / 256)), dim3(256), 0, st, ug, 0.f, (long long)nb * ldu);
     hipLaunchKernelGGL(fill_kernel, dim3((unsigned)(((long long)nb * ldz + 255) / 256)), dim3(256), 0, st, vg, 0.f, (long long)nb * ldz);
@@ -921,13 +994,32 @@ int mk_sinkhorn(const float* dsc0, const float* dsc1, const float* scr0, const f
       hipLaunchKernelGGL(sink_col_fin_kernel, dim3((ldz + 255) / 256, nb), dim3(256), 0, st, pg, vg, n1, ldz, nrc, norm2, nu_last2);
     }
     MK_CHECK_LAUNCH();
-    hipLaunchKernelGGL(sink_final_kernel, dim3((n1 + 255) / 256, n0, nb), dim3(256), 0, st, Zg, ug, vg, norm2,
-                       scr0 ? scr0 + (long long)b0 * n0 : nullptr, scr1 ? scr1 + (long long)b0 * n1 : nullptr,
+    hipLaunchKernelGGL(sink_final_kernel<KF>, dim3((n1 + 255) / 256, n0, nb), dim3(256), 0, st, Zg, ug, vg, norm2,
+                       scr0 ? (KF ? scr0 : scr0 + (long long)b0 * n0) : nullptr, scr1 ? scr1 + (long long)b0 * n1 : nullptr,
                        scores ? scores + (long long)b0 * n0 * n1 : nullptr, kp_scores ? kp_scores + (long long)b0 * n0 * n1 : nullptr,
-                       final_scores ? final_scores + (long long)b0 * n0 * n1 : nullptr, n0, n1, ldz, ldu);
+                       final_scores ? final_scores + (long long)b0 * n0 * n1 : nullptr, n0, n1, ldz, ldu, kg, K);
     MK_CHECK_LAUNCH();
   }
   return MK_OK;
+}
+
+extern "C" {
+
+int mk_sinkhorn(const float* dsc0, const float* dsc1, const float* scr0, const float* scr1, float alpha, int iters, float* scores,
+                float* kp_scores, float* final_scores, float* work, int B, int C, int n0, int n1, mk_stream_t stream) {
+  return mk_sinkhorn_kf(dsc0, dsc1, scr0, scr1, alpha, iters, scores, kp_scores, final_scores, work, B, C, n0, n1, nullptr, B, stream);
+}
+
+int mk_sinkhorn_kf(const float* dsc0, const float* dsc1, const float* scr0, const float* scr1, float alpha, int iters, float* scores,
+                   float* kp_scores, float* final_scores, float* work, int B, int C, int n0, int n1, const int* kf_index, int K,
+                   mk_stream_t stream) {
+  MK_CHECK_ARG(dsc0 && dsc1 && work && (scores || final_scores), "mk_sinkhorn: null pointer");
+  MK_CHECK_ARG(kf_index ? (K > 0 && K <= B) : K == B, "mk_sinkhorn_kf: need 0 < K <= B with a keyframe map, K == B without");
+  if (kf_index)
+    return sinkhorn_impl<true>(dsc0, dsc1, scr0, scr1, alpha, iters, scores, kp_scores, final_scores, work, B, C, n0, n1, kf_index, K,
+                               (hipStream_t)stream);
+  return sinkhorn_impl<false>(dsc0, dsc1, scr0, scr1, alpha, iters, scores, kp_scores, final_scores, work, B, C, n0, n1, nullptr, B,
+                              (hipStream_t)stream);
 }
 
 int mk_dual_softmax_set_chunks(int chunks) {

@@ -857,14 +857,19 @@ __device__ __forceinline__ void inv3(const float* K, float* o) {
   o[6] = Cc * id; o[7] = -(a * h - b * g) * id; o[8] = (a * e - b * d) * id;
 }
 
+// KF (keyframe mode): kps0 / dep0 hold K keyframes, pair b reads row kf[b] (kf_row); K0 stays per pair
+template <bool KF>
 __global__ __launch_bounds__(256) void gather_backproject_kernel(const int* __restrict__ idx, const float* __restrict__ fs,
                                                                  const float* __restrict__ kps0, const float* __restrict__ dep0,
                                                                  const float* __restrict__ kps1, const float* __restrict__ dep1,
                                                                  const float* __restrict__ K0, const float* __restrict__ K1,
                                                                  float* __restrict__ X, float* __restrict__ Y,
                                                                  float* __restrict__ wts, float* __restrict__ corr,
-                                                                 int rows_per_pair, int k, int n0, int n1) {
+                                                                 int rows_per_pair, int k, int n0, int n1, const int* __restrict__ kf,
+                                                                 int K) {
   const int r = blockIdx.y, b = r / rows_per_pair;
+  int b0;
+  if (!kf_row<KF>(kf, K, b, b0)) return;
   const int s = blockIdx.x * 256 + threadIdx.x;
   if (s >= k) return;
   float Ki0[9], Ki1[9];
@@ -872,7 +877,7 @@ __global__ __launch_bounds__(256) void gather_backproject_kernel(const int* __re
   inv3(K1 + b * 9, Ki1);
   const int c = idx[(long long)r * k + s];
   const int i = c / n1, j = c - i * n1;
-  const float u0 = kps0[((long long)b * 2 + 0) * n0 + i], v0 = kps0[((long long)b * 2 + 1) * n0 + i], d0 = dep0[(long long)b * n0 + i];
+  const float u0 = kps0[((long long)b0 * 2 + 0) * n0 + i], v0 = kps0[((long long)b0 * 2 + 1) * n0 + i], d0 = dep0[(long long)b0 * n0 + i];
   const float u1 = kps1[((long long)b * 2 + 0) * n1 + j], v1 = kps1[((long long)b * 2 + 1) * n1 + j], d1 = dep1[(long long)b * n1 + j];
   const long long o = (long long)r * k + s;
 #pragma unroll
@@ -1622,11 +1627,24 @@ int mk_exprace_topk(const float* p, const float* noise, unsigned long long seed,
 int mk_gather_backproject(const int* idx, const float* final_scores, const float* kps0, const float* depth0, const float* kps1,
                           const float* depth1, const float* K0, const float* K1, float* X, float* Y, float* wts, float* corr,
                           int B, int rows_per_pair, int k, int n0, int n1, mk_stream_t stream) {
+  return mk_gather_backproject_kf(idx, final_scores, kps0, depth0, kps1, depth1, K0, K1, X, Y, wts, corr, B, rows_per_pair, k, n0, n1,
+                                  nullptr, B, stream);
+}
+
+int mk_gather_backproject_kf(const int* idx, const float* final_scores, const float* kps0, const float* depth0, const float* kps1,
+                             const float* depth1, const float* K0, const float* K1, float* X, float* Y, float* wts, float* corr,
+                             int B, int rows_per_pair, int k, int n0, int n1, const int* kf_index, int K, mk_stream_t stream) {
   MK_CHECK_ARG(idx && final_scores && kps0 && depth0 && kps1 && depth1 && K0 && K1 && X && Y && wts && corr,
                "mk_gather_backproject: null pointer");
   MK_CHECK_ARG(B > 0 && rows_per_pair > 0 && k > 0 && n0 > 0 && n1 > 0, "mk_gather_backproject: bad sizes");
-  hipLaunchKernelGGL(gather_backproject_kernel, dim3((k + 255) / 256, B * rows_per_pair), dim3(256), 0, (hipStream_t)stream, idx,
-                     final_scores, kps0, depth0, kps1, depth1, K0, K1, X, Y, wts, corr, rows_per_pair, k, n0, n1);
+  MK_CHECK_ARG(kf_index ? (K > 0 && K <= B) : K == B, "mk_gather_backproject_kf: need 0 < K <= B with a keyframe map, K == B without");
+  const dim3 g((k + 255) / 256, B * rows_per_pair);
+  if (kf_index)
+    hipLaunchKernelGGL(gather_backproject_kernel<true>, g, dim3(256), 0, (hipStream_t)stream, idx, final_scores, kps0, depth0, kps1,
+                       depth1, K0, K1, X, Y, wts, corr, rows_per_pair, k, n0, n1, kf_index, K);
+  else
+    hipLaunchKernelGGL(gather_backproject_kernel<false>, g, dim3(256), 0, (hipStream_t)stream, idx, final_scores, kps0, depth0, kps1,
+                       depth1, K0, K1, X, Y, wts, corr, rows_per_pair, k, n0, n1, nullptr, B);
   MK_CHECK_LAUNCH();
   return MK_OK;
 }

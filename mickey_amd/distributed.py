@@ -14,8 +14,20 @@ def shard_range(n_items, rank, world):
     return lo, lo + base + (1 if rank < rem else 0)
 
 
+# per-keyframe entries of a keyframe-mode data dict (model.py: K rows, the rest of the batched entries has B)
+KEYFRAME_KEYS = ("image0", "kps0", "depth_kp0", "scr0", "dsc0", "depth0_map")
+
+
+def num_pairs(data):
+    """Pairs in a data dict: image1's rows (keyframe mode: image0 holds the K keyframes) -- image0's otherwise."""
+    return data["image1" if "keyframe_index" in data else "image0"].shape[0]
+
+
 def shard_batch(data, rank, world):
-    """Slice every batched tensor / list of a data dict to this rank's pairs."""
+    """Slice every batched tensor / list of a data dict to this rank's pairs.  Keyframe mode (data["keyframe_index"]): the rank
+    keeps only the keyframes its pairs use, in order of first use, and its keyframe_index is remapped onto them."""
+    if "keyframe_index" in data:
+        return _shard_keyframe_batch(data, rank, world)
     B = data["image0"].shape[0]
     lo, hi = shard_range(B, rank, world)
     out = {}
@@ -27,6 +39,34 @@ def shard_batch(data, rank, world):
         else:
             out[k] = v
     # global index of the shard's first pair: keys the samplers' Philox streams, so sharded == unsharded poses
+    out["pair_base"] = int(data.get("pair_base", 0)) + lo
+    return out
+
+
+def _shard_keyframe_batch(data, rank, world):
+    import numpy as np
+    B = data["image1"].shape[0]
+    kf = data["keyframe_index"]
+    kf = (kf.detach().cpu().numpy() if torch.is_tensor(kf) else np.asarray(kf)).astype(np.int64).reshape(-1)
+    if kf.shape[0] != B:
+        raise ValueError("keyframe_index must hold one entry per pair (%d), got %d" % (B, kf.shape[0]))
+    lo, hi = shard_range(B, rank, world)
+    used, local = {}, []
+    for k in kf[lo:hi].tolist():
+        local.append(used.setdefault(k, len(used)))
+    keep = list(used)   # global keyframe of each local one
+    out = {}
+    for k, v in data.items():
+        if k == "keyframe_index":
+            out[k] = torch.tensor(local, dtype=torch.int64)
+        elif k in KEYFRAME_KEYS and torch.is_tensor(v) and v.dim() > 0:
+            out[k] = v[torch.tensor(keep, dtype=torch.long, device=v.device)]
+        elif torch.is_tensor(v) and v.dim() > 0 and v.shape[0] == B:
+            out[k] = v[lo:hi]
+        elif isinstance(v, (list, tuple)) and len(v) == B:
+            out[k] = v[lo:hi]
+        else:
+            out[k] = v
     out["pair_base"] = int(data.get("pair_base", 0)) + lo
     return out
 
@@ -100,7 +140,7 @@ def _empty_poses(device):
 def forward_local(model, local, sizes, gatherer=None):
     """The second half of forward_sharded for a caller that already holds only ITS slice of the global batch (`local`, with
     `pair_base` set; `sizes` = every rank's slice length): forward (skipped for an empty slice), then the all-gather."""
-    if local["image0"].shape[0] > 0:
+    if num_pairs(local) > 0:
         R, t = model(local)
         conf = local["inliers"]
     else:
@@ -117,7 +157,7 @@ def forward_sharded(model, data, return_local=False, gatherer=None):
     takes part in the collective.  With a PoseGatherer the collective runs on its side stream."""
     rank = dist.get_rank() if dist.is_initialized() else 0
     world = dist.get_world_size() if dist.is_initialized() else 1
-    B = data["image0"].shape[0]
+    B = num_pairs(data)
     local = shard_batch(data, rank, world)
     sizes = [shard_range(B, r, world)[1] - shard_range(B, r, world)[0] for r in range(world)]
     if sizes[rank] > 0:

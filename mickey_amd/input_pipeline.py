@@ -13,7 +13,9 @@ lib/datasets/mapfree.py:108-160, submission.py:76-86: 8 workers).  At 250+ pairs
     (`correct_intrinsic_scale`, utils.py:86-99).
 
 `PairFeeder` yields `data` dicts with the keys the model reads (image0, image1, K_color0, K_color1) plus pass-through
-metadata (scene_id, pair_names), i.e. what MapFreeScene.__getitem__ + the default collate produce for inference.
+metadata (scene_id, pair_names), i.e. what MapFreeScene.__getitem__ + the default collate produce for inference.  With
+share_keyframes, records of a batch that name the same image-0 file share one decoded frame and the batch is a keyframe-mode
+batch (image0 [K, ...], keyframe_index [B]: README, "Keyframe mode").
 """
 import concurrent.futures
 import io
@@ -91,6 +93,25 @@ class FrameRing:
         return out[:, 0], out[:, 1]
 
 
+def group_keyframes(batch):
+    """Keyframe grouping of one batch of records (PairFeeder(share_keyframes=True)): -> (keyframes, keyframe_index) where
+    keyframes lists the record index that supplies each distinct image 0, in order of first appearance, and keyframe_index[b]
+    is the keyframe of record b.  Only image 0s given as file paths are merged (equal path = one frame); arrays and bytes are
+    never merged."""
+    first, keyframes, index = {}, [], []
+    for b, r in enumerate(batch):
+        src = r["image0"]
+        key = os.fspath(src) if isinstance(src, (str, os.PathLike)) else None
+        if key is None or key not in first:
+            if key is not None:
+                first[key] = len(keyframes)
+            index.append(len(keyframes))
+            keyframes.append(b)
+        else:
+            index.append(first[key])
+    return keyframes, index
+
+
 class PairFeeder:
     """Iterate device batches over a list of pair records.
 
@@ -99,10 +120,15 @@ class PairFeeder:
     All frames must share one stored size (Map-free: 540 x 720); `resize` = (W, H) the model runs at.
     """
 
-    def __init__(self, records, batch_size, resize, device="cuda:0", workers=None, slots=3, batches=None):
+    def __init__(self, records, batch_size, resize, device="cuda:0", workers=None, slots=3, batches=None, share_keyframes=False):
         """batches: explicit list of record lists (each at most batch_size long, empty ones allowed) instead of cutting
         `records` into runs of batch_size -- a rank of a sharded evaluation passes its slice of every global batch, so it
-        decodes, pins and uploads only the frames it will process; an empty slice yields a dict with 0-row tensors."""
+        decodes, pins and uploads only the frames it will process; an empty slice yields a dict with 0-row tensors.
+        share_keyframes: the records of a batch whose `image0` is the same path are decoded once (group_keyframes); the K
+        distinct frames go to ring column 0, rows [0, K), and the batch carries `keyframe_index` (keyframe mode of the model).
+        `frames_decoded` counts the frames this feeder has decoded so far."""
+        self.share_keyframes = bool(share_keyframes)
+        self.frames_decoded = 0
         self._batches = None if batches is None else [list(b) for b in batches]
         if self._batches is not None:
             records = [r for b in self._batches for r in b]
@@ -120,7 +146,10 @@ class PairFeeder:
 
     def _empty(self, H, W):
         z = lambda *s: torch.zeros(s, device=self.device)  # noqa: E731
-        return {"image0": z(0, 3, H, W), "image1": z(0, 3, H, W), "K_color0": z(0, 3, 3), "K_color1": z(0, 3, 3)}
+        out = {"image0": z(0, 3, H, W), "image1": z(0, 3, H, W), "K_color0": z(0, 3, 3), "K_color1": z(0, 3, 3)}
+        if self.share_keyframes:
+            out["keyframe_index"] = torch.zeros((0,), dtype=torch.int64)
+        return out
 
     @staticmethod
     def _decode_into(dst, src):
@@ -151,9 +180,12 @@ class PairFeeder:
                 if not ring._first[slot]:
                     ring.copied[slot].synchronize()     # the pinned buffer is free once its last upload has left it
                 futs = []
+                kfs = group_keyframes(batches[bi])[0] if self.share_keyframes else range(len(batches[bi]))
+                for i, b in enumerate(kfs):   # (without sharing: every record's own image 0, row i = record i)
+                    futs.append(pool.submit(self._decode_into, ring.host[slot][i, 0], batches[bi][b]["image0"]))
                 for i, r in enumerate(batches[bi]):
-                    futs.append(pool.submit(self._decode_into, ring.host[slot][i, 0], r["image0"]))
                     futs.append(pool.submit(self._decode_into, ring.host[slot][i, 1], r["image1"]))
+                self.frames_decoded += len(futs)
                 return slot, futs
             pending = {}
             ahead = min(self.slots - 1, len(batches))
@@ -173,10 +205,15 @@ class PairFeeder:
                     yield self._empty(H, W)
                     continue
                 im0, im1 = ring.to_model_input(slot, H, W, n)
+                if self.share_keyframes:
+                    kfs, kfi = group_keyframes(batch)
+                    im0 = im0[:len(kfs)]   # the K keyframes (rows >= K of column 0 hold stale frames: dropped here)
                 K0 = torch.stack([correct_intrinsic_scale(torch.as_tensor(r["K_color0"], dtype=torch.float32), sx, sy) for r in batch])
                 K1 = torch.stack([correct_intrinsic_scale(torch.as_tensor(r["K_color1"], dtype=torch.float32), sx, sy) for r in batch])
                 data = {"image0": im0, "image1": im1, "K_color0": K0.to(self.device, non_blocking=True),
                         "K_color1": K1.to(self.device, non_blocking=True)}
+                if self.share_keyframes:
+                    data["keyframe_index"] = torch.tensor(kfi, dtype=torch.int64)
                 for k in batch[0]:
                     if k not in data:
                         data[k] = _collate([r[k] for r in batch])

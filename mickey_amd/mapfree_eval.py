@@ -1,7 +1,7 @@
 """Map-free evaluation harness: dataset on disk -> sharded GPU inference -> `submission.zip` -> the reference evaluator.
 
     python -m mickey_amd.mapfree_eval --dataset_path data/ --split val --checkpoint mickey.ckpt -o results/ \\
-           [--config cfg.yaml] [--batch_size 32] [--evaluator_root /path/to/nianticlabs-mickey]
+           [--config cfg.yaml] [--batch_size 32] [--share_keyframes] [--evaluator_root /path/to/nianticlabs-mickey]
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 -m mickey_amd.mapfree_eval ...   (8 GPUs)
 
 What it replaces: the reference's `submission.py:70-99` (DataModule -> predict -> save_submission) for the val / test
@@ -117,11 +117,14 @@ def missing_inputs(dataset_path, split, checkpoint):
     return why
 
 
-def predict_to_zip(model, records, batch_size, resize, output_zip, sharded=False, device="cuda:0", rank=None, world=None):
+def predict_to_zip(model, records, batch_size, resize, output_zip, sharded=False, device="cuda:0", rank=None, world=None,
+                   share_keyframes=False, stats=None):
     """records -> poses -> zip (reference submission.py:32-68).  With `sharded`, every rank runs this on the same record
     LIST but feeds (decodes, pins, uploads, preprocesses) only its contiguous slice of every global batch; one all-gather
     per batch returns all poses and rank 0 writes the file.  The Philox streams are keyed by the position in the global
-    batch (`pair_base`), so the poses equal those of an unsharded run."""
+    batch (`pair_base`), so the poses equal those of an unsharded run.  share_keyframes: every batch (slice) decodes and
+    encodes each scene's keyframe once and runs the model's keyframe mode (a batch that spans a scene boundary has K = 2);
+    the poses are those of the default run.  stats (dict, optional) receives `frames_decoded` of this rank's feeder."""
     import torch
     from . import distributed as D
     from . import submission_io as sio
@@ -137,7 +140,7 @@ def predict_to_zip(model, records, batch_size, resize, output_zip, sharded=False
     gbatches = [records[i:i + batch_size] for i in range(0, len(records), batch_size)]
     spans = [[D.shard_range(len(b), r, world) for r in range(world)] for b in gbatches]
     feeder = PairFeeder(None, batch_size, resize, device=device,
-                        batches=[b[sp[rank][0]:sp[rank][1]] for b, sp in zip(gbatches, spans)])
+                        batches=[b[sp[rank][0]:sp[rank][1]] for b, sp in zip(gbatches, spans)], share_keyframes=share_keyframes)
     for data, gb, sp in zip(feeder, gbatches, spans):
         with torch.no_grad():
             if sharded:
@@ -150,6 +153,8 @@ def predict_to_zip(model, records, batch_size, resize, output_zip, sharded=False
                          t.detach().cpu().numpy(), inl.detach().cpu().numpy())
     if rank == 0:   # the rank resolved above (argument, else the process group's; 0 when not sharded)
         sio.save_submission(results, output_zip)
+    if stats is not None:
+        stats["frames_decoded"] = feeder.frames_decoded
     return results
 
 
@@ -180,6 +185,8 @@ def main(argv=None):
     ap.add_argument("--output_root", "-o", default="results/")
     ap.add_argument("--batch_size", type=int, default=32)
     ap.add_argument("--scenes", nargs="*", default=None)
+    ap.add_argument("--share_keyframes", action="store_true",
+                    help="decode and encode each scene's keyframe once per batch (model keyframe mode; same poses)")
     ap.add_argument("--evaluator_root", default=os.environ.get("MICKEY_REFERENCE_ROOT"))
     args = ap.parse_args(argv)
 
@@ -206,8 +213,11 @@ def main(argv=None):
     model = build_model(cfg, args.checkpoint).to("cuda:%d" % local)
     records = dataset_records(args.dataset_path, args.split, resize, args.scenes)
     out_zip = Path(args.output_root) / "submission.zip"
-    predict_to_zip(model, records, args.batch_size, resize, out_zip, sharded=world > 1, device="cuda:%d" % local)
-    summary = {"skipped": False, "pairs": len(records), "submission": str(out_zip), "n_gpus": world}
+    stats = {}
+    predict_to_zip(model, records, args.batch_size, resize, out_zip, sharded=world > 1, device="cuda:%d" % local,
+                   share_keyframes=args.share_keyframes, stats=stats)
+    summary = {"skipped": False, "pairs": len(records), "submission": str(out_zip), "n_gpus": world,
+               "frames_decoded": stats["frames_decoded"]}
     if int(os.environ.get("RANK", "0")) == 0:
         metrics, msg = run_evaluator(args.evaluator_root, out_zip, args.dataset_path, args.split)
         summary["evaluator"] = msg

@@ -258,15 +258,35 @@ class MickeyRelativePose(nn.Module):
         return self._dev_weights
 
     # ---- forward ---------------------------------------------------------------------------------
+    def _keyframe_map(self, data):
+        """Keyframe mode (data["keyframe_index"]): validate the pair -> keyframe map on the host (ValueError: wrong length, not
+        integers, out of [0, K)) and return the model's device int32 copy of it (workspace).  A map given as a device tensor is
+        copied to the host for the check: one synchronisation.  None without the key."""
+        if "keyframe_index" not in data:
+            return None
+        from . import ops
+        B, K = int(data["image1"].shape[0]), int(data["image0"].shape[0])
+        host = torch.from_numpy(ops.check_keyframe_index(data["keyframe_index"], B, K))
+        kf = self._ws.get("keyframe_index", (B,), torch.int32, self._anchor.device)
+        kf.copy_(host)
+        return kf
+
     @torch.no_grad()
-    def compute_correspondences(self, data):
-        """reference compute_correspondences.py:52-92 + compute_pose.py:23: fills the data dict."""
+    def compute_correspondences(self, data, _kf=None):
+        """reference compute_correspondences.py:52-92 + compute_pose.py:23: fills the data dict.  Keyframe mode
+        (data["keyframe_index"], README): image0 holds K distinct keyframes, image1 one query frame per pair; the per-keyframe
+        outputs (kps0, depth_kp0, scr0, dsc0, depth0_map) get K rows, the per-pair ones B."""
+        if _kf is None:
+            _kf = self._keyframe_map(data)   # validated before anything is launched
         W = self.device_weights()
         dev = self._anchor.device
         im0 = data["image0"].to(device=dev, dtype=torch.float32)
         im1 = data["image1"].to(device=dev, dtype=torch.float32)
         B = im0.shape[0]
         same = im0.shape == im1.shape
+        if _kf is not None:   # K keyframes + B queries: one pass over K + B images when the frame sizes agree
+            same = im0.shape[1:] == im1.shape[1:]
+        rows = (B, B) if _kf is None else (B, im1.shape[0])   # rows of the image-0 / image-1 outputs
         # one 2B-image pass when shapes agree (the two image sets are patched into one token matrix: no copy of the images)
         im0, im1 = (t if t.stride(3) == 1 else t.contiguous() for t in (im0, im1))   # the patch kernel takes any outer strides
         imgs = [(im0, im1)] if same else [(im0,), (im1,)]
@@ -283,18 +303,19 @@ class MickeyRelativePose(nn.Module):
             outs.append((scr, kps, depth, dsc, gh, gw))
         if same:
             scr, kps, depth, dsc, gh, gw = outs[0]
-            parts = [(scr[:B], kps[:B], depth[:B], dsc[:B], gh, gw), (scr[B:], kps[B:], depth[B:], dsc[B:], gh, gw)]
+            parts = [(scr[:B], kps[:B], depth[:B], dsc[:B], gh, gw), (scr[B:], kps[B:], depth[B:], dsc[B:], gh, gw)]   # (B = image0's rows: K in keyframe mode)
         else:
             parts = outs
         for i, (scr, kps, depth, dsc, gh, gw) in enumerate(parts):
             data["kps%d_shape" % i] = [gh, gw]
-            data["depth%d_map" % i] = depth.reshape(B, 1, gh, gw)
+            data["depth%d_map" % i] = depth.reshape(rows[i], 1, gh, gw)
             data["kps%d" % i] = kps.contiguous()
             data["depth_kp%d" % i] = depth.contiguous()
             data["scr%d" % i] = scr.contiguous()
             data["dsc%d" % i] = dsc.contiguous()
         data["down_factor"] = self.cfg["MICKEY"]["DINOV2"]["DOWN_FACTOR"]
-        scores, kp, fin = pipeline.match(W, self.cfg, data["dsc0"], data["dsc1"], data["scr0"], data["scr1"], self.lean)
+        scores, kp, fin = pipeline.match(W, self.cfg, data["dsc0"], data["dsc1"], data["scr0"], data["scr1"], self.lean,
+                                         keyframe_index=_kf)
         if scores is not None:
             data["scores"] = scores
             data["kp_scores"] = kp
@@ -312,7 +333,9 @@ class MickeyRelativePose(nn.Module):
         return v
 
     @torch.no_grad()
-    def estimate_pose(self, data, return_inliers=False):
+    def estimate_pose(self, data, return_inliers=False, _kf=None):
+        if _kf is None:
+            _kf = self._keyframe_map(data)
         dev = self._anchor.device
         K0 = data["K_color0"].to(device=dev, dtype=torch.float32).contiguous()
         K1 = data["K_color1"].to(device=dev, dtype=torch.float32).contiguous()
@@ -326,14 +349,15 @@ class MickeyRelativePose(nn.Module):
         # shard offset so that the poses do not depend on the sharding (mickey_amd.distributed.shard_batch sets it)
         sol = pipeline.solve(self.cfg, data["final_scores"], data["kps0"], data["depth_kp0"], data["kps1"], data["depth_kp1"],
                              K0, K1, seed=self.seed, offset=0, offset_dev=self._ctr, pair_base=int(data.get("pair_base", 0)),
-                             ws=self._ws)
+                             ws=self._ws, keyframe_index=_kf)
         if return_inliers:
             return sol["R"], sol["t"], sol["inliers"], pipeline.inliers_list(sol)
         return sol["R"], sol["t"], sol["inliers"]
 
     def _forward_eager(self, data, return_inliers=False):
-        self.compute_correspondences(data)   # a missing / failing HIP library raises _native.MickeyHipError: never papered over
-        res = self.estimate_pose(data, return_inliers)
+        kf = self._keyframe_map(data)   # keyframe mode: the map is checked on the host before any launch
+        self.compute_correspondences(data, _kf=kf)   # a missing / failing HIP library raises _native.MickeyHipError: never papered over
+        res = self.estimate_pose(data, return_inliers, _kf=kf)
         if return_inliers:
             data["inliers_list"] = res[3]
         data["R"], data["t"], data["inliers"] = res[0], res[1], res[2]
@@ -357,6 +381,8 @@ class MickeyRelativePose(nn.Module):
     def _wants_graph(self, data, return_inliers):
         mode = self.graph_mode
         if mode is False or str(mode).lower() in ("false", "0", "off") or return_inliers:
+            return False
+        if "keyframe_index" in data:   # keyframe mode runs eager (K == B would pass the shape test below)
             return False
         if self._anchor.device.type != "cuda" or not all(torch.is_tensor(data.get(k)) for k in self._GRAPH_INPUTS):
             return False

@@ -2,6 +2,7 @@
 with torch (device memory only), passes raw pointers + the current HIP stream to libmickey_hip.so and
 returns tensors.  No arithmetic happens here."""
 
+import numpy as np
 import torch
 
 
@@ -334,28 +335,78 @@ def dual_softmax_split_ok(C, temperature):
     return C == 128 and temperature > 0 and LOG2E / float(temperature) <= 100.0
 
 
+def check_keyframe_index(index, B, K):
+    """Host validation of a pair -> keyframe map (keyframe mode, mickey_hip.h: the *_kf entry points): B integers in [0, K).
+    Accepts a list, a numpy array or a CPU / device integer tensor (a device tensor is copied to the host: one synchronisation).
+    Returns the map as a numpy int32 array; raises ValueError on a wrong length, a non-integer dtype, an entry out of range or
+    more keyframes than pairs (K <= B is what the matchers' work sizes assume, mickey_hip.h)."""
+    if torch.is_tensor(index):
+        if index.dtype.is_floating_point or index.dtype.is_complex or index.dtype == torch.bool:
+            raise ValueError("keyframe_index must hold integers, got %s" % index.dtype)
+        a = index.detach().cpu().numpy()
+    else:
+        a = np.asarray(index)
+        if a.size == 0 and a.dtype == np.float64:   # [] -> an empty integer map (the length check below decides)
+            a = a.astype(np.int64)
+        if a.dtype.kind not in "iu":
+            raise ValueError("keyframe_index must hold integers, got %s" % a.dtype)
+    if a.ndim != 1 or a.shape[0] != int(B):
+        raise ValueError("keyframe_index must hold one entry per pair (%d), got shape %s" % (int(B), tuple(a.shape)))
+    if not 0 < int(K) <= max(1, int(B)):
+        raise ValueError("keyframe mode needs 1 <= K <= B keyframes (image0 has %d for %d pairs: a keyframe no pair uses is "
+                         "wasted work)" % (int(K), int(B)))
+    if a.size and (int(a.min()) < 0 or int(a.max()) >= int(K)):
+        raise ValueError("keyframe_index entries must lie in [0, %d), got [%d, %d]" % (int(K), int(a.min()), int(a.max())))
+    return a.astype(np.int32)
+
+
+def _kf_arg(keyframe_index, B, K, dev):
+    """-> (device int32 map or None, K for the ABI).  A contiguous int32 device tensor of B entries is passed as it is (the
+    caller validated it: pipeline / model; a kernel skips a pair whose entry is outside [0, K) and reads nothing for it);
+    anything else is validated on the host here and uploaded."""
+    if keyframe_index is None:
+        return None, B
+    t = keyframe_index
+    if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and t.dim() == 1 and t.shape[0] == B):
+        t = torch.from_numpy(check_keyframe_index(t, B, K)).to(dev)
+    return t, K
+
+
 def dual_softmax(dsc0, dsc1, scr0=None, scr1=None, temperature=0.1, dustbin=None, want_scores=True, want_kp=True,
-                 want_final=True, split=False):
+                 want_final=True, split=False, keyframe_index=None):
     """Returns (scores, kp_scores, final_scores) (None where not requested).  split: the correlation on the 16-bit matrix
-    cores with split-fp16 operands (mk_dual_softmax_split; unit-norm descriptors only), else the exact fp32 MFMA."""
+    cores with split-fp16 operands (mk_dual_softmax_split; unit-norm descriptors only), else the exact fp32 MFMA.
+    keyframe_index (keyframe mode): B pair -> keyframe entries; dsc0 / scr0 then hold the K keyframes, dsc1 / scr1 the B
+    pairs' query frames, and pair b correlates dsc0[keyframe_index[b]] with dsc1[b] (mk_dual_softmax_kf / _split_kf)."""
     _chk(dsc0, torch.float32)
     _chk(dsc1, torch.float32)
-    B, C, n0 = dsc0.shape
-    n1 = dsc1.shape[2]
+    K, C, n0 = dsc0.shape
+    B, n1 = dsc1.shape[0], dsc1.shape[2]
+    if keyframe_index is None:
+        assert K == B, "dsc0 and dsc1 hold different batch counts (keyframe mode needs keyframe_index)"
     dev = dsc0.device
+    kf, kfn = _kf_arg(keyframe_index, B, K, dev)
     mk = lambda want: torch.empty((B, n0, n1), device=dev, dtype=torch.float32) if want else None  # noqa: E731
     scores = mk(want_scores)
     kp = mk(want_kp and scr0 is not None)
     fin = mk(want_final and scr0 is not None)
     if split:
         work = torch.empty((query("mk_dual_softmax_split_work_floats", B, n0, n1),), device=dev, dtype=torch.float32)
-        call("mk_dual_softmax_split", ptr(dsc0), ptr(dsc1), ptr(scr0), ptr(scr1), 1.0 / float(temperature), int(dustbin is not None),
-             float(dustbin) if dustbin is not None else 0.0, ptr(scores), ptr(kp), ptr(fin), ptr(work), B, C, n0, n1, stream())
+        args = (ptr(dsc0), ptr(dsc1), ptr(scr0), ptr(scr1), 1.0 / float(temperature), int(dustbin is not None),
+                float(dustbin) if dustbin is not None else 0.0, ptr(scores), ptr(kp), ptr(fin), ptr(work), B, C, n0, n1)
+        if kf is None:
+            call("mk_dual_softmax_split", *args, stream())
+        else:
+            call("mk_dual_softmax_split_kf", *args, ptr(kf), kfn, stream())
         return scores, kp, fin
     work = torch.empty((query("mk_dual_softmax_work_floats", B, n0, n1, int(scores is None and fin is None)),), device=dev,
                        dtype=torch.float32)
-    call("mk_dual_softmax", ptr(dsc0), ptr(dsc1), ptr(scr0), ptr(scr1), 1.0 / float(temperature), int(dustbin is not None),
-         float(dustbin) if dustbin is not None else 0.0, ptr(scores), ptr(kp), ptr(fin), ptr(work), B, C, n0, n1, stream())
+    args = (ptr(dsc0), ptr(dsc1), ptr(scr0), ptr(scr1), 1.0 / float(temperature), int(dustbin is not None),
+            float(dustbin) if dustbin is not None else 0.0, ptr(scores), ptr(kp), ptr(fin), ptr(work), B, C, n0, n1)
+    if kf is None:
+        call("mk_dual_softmax", *args, stream())
+    else:
+        call("mk_dual_softmax_kf", *args, ptr(kf), kfn, stream())
     return scores, kp, fin
 
 
@@ -369,16 +420,24 @@ def sinkhorn_set_group(pairs):
     call("mk_sinkhorn_set_group", int(pairs))
 
 
-def sinkhorn(dsc0, dsc1, alpha, iters=10, scr0=None, scr1=None, want_scores=True, want_kp=False, want_final=False):
-    """Returns scores, or (scores, kp_scores, final_scores) when scr0/scr1 are given."""
-    B, C, n0 = dsc0.shape
-    n1 = dsc1.shape[2]
+def sinkhorn(dsc0, dsc1, alpha, iters=10, scr0=None, scr1=None, want_scores=True, want_kp=False, want_final=False,
+             keyframe_index=None):
+    """Returns scores, or (scores, kp_scores, final_scores) when scr0/scr1 are given.  keyframe_index: as in dual_softmax
+    (mk_sinkhorn_kf)."""
+    K, C, n0 = dsc0.shape
+    B, n1 = dsc1.shape[0], dsc1.shape[2]
+    if keyframe_index is None:
+        assert K == B, "dsc0 and dsc1 hold different batch counts (keyframe mode needs keyframe_index)"
     dev = dsc0.device
+    kf, kfn = _kf_arg(keyframe_index, B, K, dev)
     mk = lambda want: torch.empty((B, n0, n1), device=dev, dtype=torch.float32) if want else None  # noqa: E731
     out, kp, fin = mk(want_scores), mk(want_kp and scr0 is not None), mk(want_final and scr0 is not None)
     work = torch.empty((query("mk_sinkhorn_work_floats", B, n0, n1),), device=dev, dtype=torch.float32)
-    call("mk_sinkhorn", ptr(dsc0), ptr(dsc1), ptr(scr0), ptr(scr1), float(alpha), int(iters), ptr(out), ptr(kp), ptr(fin),
-         ptr(work), B, C, n0, n1, stream())
+    args = (ptr(dsc0), ptr(dsc1), ptr(scr0), ptr(scr1), float(alpha), int(iters), ptr(out), ptr(kp), ptr(fin), ptr(work), B, C, n0, n1)
+    if kf is None:
+        call("mk_sinkhorn", *args, stream())
+    else:
+        call("mk_sinkhorn_kf", *args, ptr(kf), kfn, stream())
     return out if scr0 is None else (out, kp, fin)
 
 
@@ -450,17 +509,24 @@ def _c(*ts):
     return [None if t is None else t.contiguous() for t in ts]
 
 
-def gather_backproject(idx, final_scores, kps0, depth0, kps1, depth1, K0, K1, rows_per_pair):
+def gather_backproject(idx, final_scores, kps0, depth0, kps1, depth1, K0, K1, rows_per_pair, keyframe_index=None):
+    """keyframe_index (keyframe mode, mk_gather_backproject_kf): kps0 / depth0 hold the K keyframes, pair b reads row
+    keyframe_index[b]; K0 stays per pair."""
     idx, final_scores, kps0, depth0, kps1, depth1, K0, K1 = _c(idx, final_scores, kps0, depth0, kps1, depth1, K0, K1)
     B, n0, n1 = final_scores.shape
     R, k = idx.shape
     dev = idx.device
+    kf, kfn = _kf_arg(keyframe_index, B, kps0.shape[0], dev)
     X = torch.empty((R, k, 3), device=dev, dtype=torch.float32)
     Y = torch.empty((R, k, 3), device=dev, dtype=torch.float32)
     wts = torch.empty((R, k), device=dev, dtype=torch.float32)
     corr = torch.empty((R, k, 6), device=dev, dtype=torch.float32)
-    call("mk_gather_backproject", ptr(idx), ptr(final_scores), ptr(kps0), ptr(depth0), ptr(kps1), ptr(depth1), ptr(K0),
-         ptr(K1), ptr(X), ptr(Y), ptr(wts), ptr(corr), B, rows_per_pair, k, n0, n1, stream())
+    args = (ptr(idx), ptr(final_scores), ptr(kps0), ptr(depth0), ptr(kps1), ptr(depth1), ptr(K0), ptr(K1), ptr(X), ptr(Y),
+            ptr(wts), ptr(corr), B, rows_per_pair, k, n0, n1)
+    if kf is None:
+        call("mk_gather_backproject", *args, stream())
+    else:
+        call("mk_gather_backproject_kf", *args, ptr(kf), kfn, stream())
     return X, Y, wts, corr
 
 

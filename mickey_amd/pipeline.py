@@ -279,8 +279,10 @@ def heads_forward(W, ws, feat, nimg, gh, gw, cfg):
                           down=float(mk["DINOV2"]["DOWN_FACTOR"]))
 
 
-def match(W, cfg, dsc0, dsc1, scr0, scr1, lean=False):
+def match(W, cfg, dsc0, dsc1, scr0, scr1, lean=False, keyframe_index=None):
+    """keyframe_index (keyframe mode): int32 device map pair -> row of dsc0 / scr0 (which then hold the K keyframes)."""
     fm = cfg["FEATURE_MATCHER"]
+    kf = {} if keyframe_index is None else {"keyframe_index": keyframe_index}   # (the standard call keeps its exact signature)
     if fm["TYPE"] == "DualSoftmax":
         ds = fm["DUAL_SOFTMAX"]
         # AMD.MATCHER_CORR: 'auto' = the split-fp16 correlation on the 16-bit matrix cores when its preconditions hold
@@ -290,21 +292,22 @@ def match(W, cfg, dsc0, dsc1, scr0, scr1, lean=False):
         if mode == "split16" and not can:
             raise ValueError("AMD.MATCHER_CORR: split16 needs MICKEY.DSC_HEAD.NORM_DSC, 128 descriptor channels and T >= 0.0145")
         return ops.dual_softmax(dsc0, dsc1, scr0, scr1, float(ds["TEMPERATURE"]), W.dustbin if ds["USE_DUSTBIN"] else None,
-                                want_scores=not lean, want_kp=not lean, want_final=True, split=can and mode != "fp32")
+                                want_scores=not lean, want_kp=not lean, want_final=True, split=can and mode != "fp32", **kf)
     if fm["TYPE"] == "Sinkhorn":
         # the reference's Sinkhorn branch is unreachable through featureMatcher.forward; the maths
         # restated is feature_matcher.py:125-137 with matching_mat(dsc0, dsc1, None)
         alpha = W.dustbin if W.dustbin is not None else float(fm["SINKHORN"]["DUSTBIN_SCORE_INIT"])
         return ops.sinkhorn(dsc0, dsc1, alpha, int(fm["SINKHORN"]["NUM_IT"]), scr0, scr1, want_scores=not lean,
-                            want_kp=not lean, want_final=True)
+                            want_kp=not lean, want_final=True, **kf)
     raise ValueError("feature matcher not recognized: %r" % (fm["TYPE"],))
 
 
 def solve(cfg, final_scores, kps0, depth0, kps1, depth1, K0, K1, seed=0, offset=0, noise_outer=None, noise_inner=None,
-          idx3_in=None, debug=False, offset_dev=None, pair_base=0, ws=None):
+          idx3_in=None, debug=False, offset_dev=None, pair_base=0, ws=None, keyframe_index=None):
     """reference probabilisticProcrustes.py:183-348 on device.  Returns a dict with R [B,3,3], t [B,1,3],
     inliers [B,1] and the intermediates needed for the inlier list.  pair_base = global index of pair 0 (keys the
-    Philox streams: sharding a batch over calls / GPUs does not change any pair's draws)."""
+    Philox streams: sharding a batch over calls / GPUs does not change any pair's draws).  keyframe_index (keyframe mode):
+    int32 device map pair -> row of kps0 / depth0 (which then hold the K keyframes); K0 stays per pair."""
     P = cfg["PROCRUSTES"]
     it_m, it_r, ns, k3 = int(P["IT_MATCHES"]), int(P["IT_RANSAC"]), int(P["NUM_SAMPLED_MATCHES"]), int(P["NUM_CORR_3D_3D"])
     if k3 != 3:
@@ -322,7 +325,8 @@ def solve(cfg, final_scores, kps0, depth0, kps1, depth1, K0, K1, seed=0, offset=
             work = ws.bufs[key] = ops.exprace_work(B, it_m, ns, n0 * n1, dev)
     idx, cnt = ops.exprace_topk(final_scores.reshape(B, n0 * n1), it_m, ns, noise=noise_outer, seed=seed, offset=offset,
                                 invalid=invalid, offset_dev=offset_dev, pair_base=pair_base, work=work)
-    X, Y, w, corr = ops.gather_backproject(idx, final_scores, kps0, depth0, kps1, depth1, K0, K1, it_m)
+    X, Y, w, corr = ops.gather_backproject(idx, final_scores, kps0, depth0, kps1, depth1, K0, K1, it_m,
+                                           **({} if keyframe_index is None else {"keyframe_index": keyframe_index}))
     Rh, th, score, idx3 = ops.ransac_hypotheses(X, Y, w, it_r, float(P["TH_SOFT_INLIER"]), noise3=noise_inner,
                                                 idx3_in=idx3_in, seed=seed, offset=offset + 1, offset_dev=offset_dev,
                                                 set_base=pair_base * it_m)
