@@ -323,6 +323,32 @@ int mk_sinkhorn_kf(const float* dsc0, const float* dsc1, const float* scr0, cons
                    float* scores, float* kp_scores, float* final_scores, float* work, int B, int C, int n0, int n1,
                    const int* kf_index, int K, mk_stream_t stream);
 
+/* Training: the dual softmax with its backward (reference lib/models/MicKey/model.py:124-134 back-propagates d loss / d final_scores
+ * through final_scores = dualSoftmax(dsc0, dsc1) * kp_matrix_scores: feature_matcher.py:64-83, compute_correspondences.py:46-50,
+ * model.py:201).  C == 128; split != 0 selects the split-fp16 correlation (preconditions of mk_dual_softmax_split), else exact fp32.
+ *
+ * mk_dual_softmax_train: the forward.  scores / kp_scores / final_scores are those of mk_dual_softmax (split = 0) /
+ *   mk_dual_softmax_split (split = 1) on the same inputs, bit for bit (at least one of scores, final_scores non-NULL).
+ *   dustbin: DEVICE pointer to the fp32 dustbin scalar (feature_matcher.py:60: a trainable Parameter; no host synchronisation),
+ *            NULL = no dustbin.
+ *   lse [B, 2, max(n0, n1)] fp32, written: the merged log-sums of the augmented matrix in the LOG2 domain, lse[b][0][i] =
+ *            log2 sum_j 2^(S_ij log2 e) over row i (dustbin column included), lse[b][1][j] the same over column j; S = dsc0^T dsc1 / T.
+ *   work: mk_dual_softmax_train_work_floats(B, n0, n1, split) fp32 elements, 16-byte aligned. */
+long long mk_dual_softmax_train_work_floats(int B, int n0, int n1, int split);
+int mk_dual_softmax_train(const float* dsc0, const float* dsc1, const float* scr0, const float* scr1, float inv_temperature,
+                          const float* dustbin, float* scores, float* kp_scores, float* final_scores, float* lse, float* work, int B,
+                          int C, int n0, int n1, int split, mk_stream_t stream);
+/* mk_dual_softmax_bwd: the backward of final_scores (scr0 / scr1 given) or of scores (both NULL).
+ *   Inputs as given to mk_dual_softmax_train (same split), its lse, and G [B, n0, n1] fp32 = d loss / d final_scores (or / d scores).
+ *   Outputs, each may be NULL (not computed): g_dsc0 [B, C, n0], g_dsc1 [B, C, n1], g_scr0 [B, n0], g_scr1 [B, n1] (need scores),
+ *   g_dustbin [B] (needs the dustbin): one value per pair, the caller sums them.  Outputs are overwritten, not accumulated.
+ *   Deterministic and batch-invariant: no atomics, every reduction in a fixed order, pair b's values do not depend on B.
+ *   work: mk_dual_softmax_bwd_work_floats(B, n0, n1, split) fp32 elements, 16-byte aligned. */
+long long mk_dual_softmax_bwd_work_floats(int B, int n0, int n1, int split);
+int mk_dual_softmax_bwd(const float* dsc0, const float* dsc1, const float* scr0, const float* scr1, float inv_temperature,
+                        const float* dustbin, const float* lse, const float* G, float* g_dsc0, float* g_dsc1, float* g_scr0,
+                        float* g_scr1, float* g_dustbin, float* work, int B, int C, int n0, int n1, int split, mk_stream_t stream);
+
 /* featureMatcher.get_matches_list (feature_matcher.py:19-46), batched: mutual nearest neighbours on
  * scores[b, :n0-1, :n1-1], sorted by score descending.  matches int32 [B, n0, 2] (row i, col j),
  * count int32 [B].  work: 2*B*(n0+n1) ints. */

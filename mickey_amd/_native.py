@@ -58,6 +58,10 @@ SIGNATURES = {
     "mk_dual_softmax_split_kf": ("i", "ppppfifppppiiiipip"),
     "mk_sinkhorn_kf": ("i", "ppppfippppiiiipip"),
     "mk_mutual_nn": ("i", "ppppiiip"),
+    "mk_dual_softmax_train_work_floats": ("l", "iiii"),
+    "mk_dual_softmax_train": ("i", "ppppfppppppiiiiip"),
+    "mk_dual_softmax_bwd_work_floats": ("l", "iiii"),
+    "mk_dual_softmax_bwd": ("i", "ppppfpppppppppiiiiip"),
     "mk_exprace_topk_work_bytes": ("l", "iiil"),
     "mk_exprace_topk_state_bytes": ("l", "ii"),
     "mk_exprace_topk": ("i", "ppuupppppiiliip"),

@@ -14,14 +14,13 @@
 // Sinkhorn (feature_matcher.py:93-137) and mutual-NN (:19-46) follow below.
 #include <type_traits>
 
-#include "mk_common.hpp"
+#include "mk_matcher.hpp"
 
 namespace {
 using namespace mk;
+using namespace mk::ds;
 
-constexpr int MT = 64;      // tile edge
-constexpr int NCHUNK = 4;   // column chunks of pass 1
-constexpr int CMAX = 128;   // descriptor channels held in LDS
+constexpr int MT = 64;      // tile edge (Sinkhorn couplings)
 
 // stage dsc[b][c][i0 .. i0+63] (c < C) into s[c][64]; columns >= n are zero
 __device__ __forceinline__ void stage_desc(float* s, const float* __restrict__ dsc, int C, int n, int i0) {
@@ -46,88 +45,7 @@ __device__ __forceinline__ f32x16 corr_tile(const float* sA, const float* sB, in
   return acc;
 }
 
-// ---- dual softmax: register-resident correlation ---------------------------------------------------------------
-// v_mfma_f32_32x32x2_f32 takes ONE float per lane per operand (lane l: row/column l & 31, k = 2 kk + (l >> 5)), so a
-// wave keeps the descriptors of its 32 rows in 64 VGPRs for its whole life and streams 32-column tiles of the other
-// image straight from L2 (descriptors are ~1 MB per image): 64 coalesced 4-byte loads + 64 MFMAs per tile, no LDS, no
-// barriers.  (The previous version staged 64 KiB through LDS with scalar loads per 64x64 tile and ran at ~10 % of the
-// fp32 matrix rate.)  Everything is kept in the log2 domain: v2 = S / T * log2(e), exp2 is one v_exp_f32.
-constexpr int RT = 32;       // rows per wave, columns per streamed tile
-
-__device__ __forceinline__ void lse2_merge(float& m, float& s, float m2, float s2) {
-  const float M = fmaxf(m, m2);
-  s = s * __builtin_amdgcn_exp2f(m - M) + s2 * __builtin_amdgcn_exp2f(m2 - M);
-  m = M;
-}
-
-// A-side operand: this lane's 64 k-values of row i0 + (lane & 31); rows >= n are zero
-template <bool FULLC>
-__device__ __forceinline__ void load_operand(float (&a)[CMAX / 2], const float* __restrict__ d, int C, int n, int i, int hi) {
-  const bool ok = i < n;
-  const float* pa = d + (long long)hi * n + (ok ? i : n - 1);
-#pragma unroll
-  for (int kk = 0; kk < CMAX / 2; ++kk) {
-    if (!FULLC && kk >= (C >> 1)) {
-      a[kk] = 0.f;
-    } else {
-      const float v = pa[(long long)kk * 2 * n];
-      a[kk] = ok ? v : 0.f;
-    }
-  }
-}
-
-// XCD-aware decode of a 1-D grid into (bx, by, unit): workgroups are dealt round-robin to the 8 XCDs, so the linear id
-// is re-read as (xcd, slot) and ALL gx*gy workgroups of a unit (an image pair [x side]) land on one XCD, whose 4-MiB L2
-// then holds that unit's ~2 MB of descriptors.  (Dealt naively, every XCD serves 8 pairs at a time, thrashes its L2 and
-// pulls 1.9 GB of 128-byte pieces from memory per pass: measured 1.9 ms instead of 0.4.)  The grid is padded to a
-// multiple of 8 units; returns false for padding.
-// Y_FASTEST: consecutive workgroups of a unit walk the y index (the column chunks of the split passes) first: the workgroups
-// in flight at one time then cover WHOLE rows of the output between them (kernels that write [rows, n1] matrices tile by tile:
-// a wave's 256-byte row pieces meet their neighbours' in the same DRAM pages while those are open).
-template <bool Y_FASTEST = false>
-__device__ __forceinline__ bool decode_unit_grid(int gx, int gy, int nunits, int& bx, int& by, int& unit) {
-  const int L = blockIdx.x, per = gx * gy;
-  int within;
-  if (nunits < 8) {   // too few units to give every XCD one: spread each unit over the whole chip instead
-    unit = L / per;
-    within = L - unit * per;
-  } else {
-    const int xcd = L & 7, slot = L >> 3;
-    unit = (slot / per) * 8 + xcd;
-    within = slot - (slot / per) * per;
-  }
-  if (Y_FASTEST) {
-    by = within % gy;
-    bx = within / gy;
-  } else {
-    bx = within % gx;
-    by = within / gx;
-  }
-  return unit < nunits;
-}
-
-// Scheduling directive for the tile body (one basic block): all 64 operand loads first, then the 64 MFMAs.  Left alone,
-// the scheduler keeps ONE operand register and emits load -> s_waitcnt vmcnt(0) -> MFMA, i.e. 64 serial memory round
-// trips per tile (measured 32 us per tile instead of ~3).
-#define MK_LOADS_THEN_MFMAS()                                  \
-  do {                                                         \
-    __builtin_amdgcn_sched_group_barrier(0x020, CMAX / 2, 0);  \
-    __builtin_amdgcn_sched_group_barrier(0x002, CMAX / 2, 0);  \
-    __builtin_amdgcn_sched_group_barrier(0x008, CMAX / 2, 0);  \
-  } while (0)
-
-template <bool FULLC>
-__device__ __forceinline__ f32x16 corr_regs(const float (&a)[CMAX / 2], const float (&bq)[CMAX / 2], int C) {
-  f32x16 acc;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) acc[i] = 0.f;
-#pragma unroll
-  for (int kk = 0; kk < CMAX / 2; ++kk) {
-    if (FULLC || kk < (C >> 1)) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[kk], bq[kk], acc, 0, 0, 0);
-  }
-  return acc;
-}
-
+// ---- dual softmax, exact path (helpers: mk_matcher.hpp) ---------------------------------------------------------
 // pass 1.  grid (row blocks of 128, NCHUNK, B), one wave per 32 rows and one chunk of columns.  ONE correlation serves
 // both softmax directions (round 1 ran it twice, once for S and once for S^T):
 //   * rows of S: per-lane online (max, sum) over the columns this lane sees, merged across the 32 lanes at the end;
@@ -294,11 +212,6 @@ __global__ __launch_bounds__(256) void dual_softmax_apply_kernel(const float* vb
 //          running maximum: one v_exp_f32 per element;
 //   merge  lse_final_kernel as for the exact path (partials carry max = 0);
 //   pass 2 the SAME correlation again (bit-identical accumulators) -> scores, kp_scores, final_scores straight from registers.
-constexpr int SP_KS = 8;        // K steps of 16 channels: C = 128
-constexpr int SP_BLK_U4 = SP_KS * 2 * 64;   // uint4 per block of 32 keypoints (16 KiB)
-constexpr int NCHUNK_S = 8;     // column chunks of the split passes (FIXED: the summation order of a row does not depend on B)
-constexpr float SP_SCALE = 1024.0f;
-
 // fp32 [B, C = 128, n] -> split planes [B, nblk, 8, 2, 64] x 16 B.  grid (nblk, B), 512 threads: thread = (K step, lane)
 __global__ __launch_bounds__(512) void dsc_split_kernel(const float* __restrict__ dsc, uint4* __restrict__ planes, int n, int nblk) {
   const int blk = blockIdx.x, b = blockIdx.y;
@@ -316,34 +229,6 @@ __global__ __launch_bounds__(512) void dsc_split_kernel(const float* __restrict_
   uint4* o = planes + ((long long)b * nblk + blk) * SP_BLK_U4 + (st * 2) * 64 + l;
   o[0] = __builtin_bit_cast(uint4, h);
   o[64] = __builtin_bit_cast(uint4, lo);
-}
-
-struct SplitOperand {
-  uint4 h[SP_KS], l[SP_KS];
-  __device__ __forceinline__ void load(const uint4* __restrict__ blk, int lane) {
-#pragma unroll
-    for (int st = 0; st < SP_KS; ++st) {
-      h[st] = blk[(st * 2) * 64 + lane];
-      l[st] = blk[(st * 2 + 1) * 64 + lane];
-    }
-  }
-};
-
-// S' = 2^20 x (32 rows of a) . (32 columns of b): cross terms first, the large term last
-__device__ __forceinline__ f32x16 corr_split(const SplitOperand& a, const SplitOperand& b) {
-  f32x16 acc;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) acc[i] = 0.f;
-#pragma unroll
-  for (int st = 0; st < SP_KS; ++st)
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a.l[st]), __builtin_bit_cast(f16x8, b.h[st]), acc, 0, 0, 0);
-#pragma unroll
-  for (int st = 0; st < SP_KS; ++st)
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a.h[st]), __builtin_bit_cast(f16x8, b.l[st]), acc, 0, 0, 0);
-#pragma unroll
-  for (int st = 0; st < SP_KS; ++st)
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a.h[st]), __builtin_bit_cast(f16x8, b.h[st]), acc, 0, 0, 0);
-  return acc;
 }
 
 // pass 1.  grid: decode_unit_grid(gx = row blocks / 4, NCHUNK_S, B); one wave per 32 rows and one chunk of column tiles.
@@ -785,11 +670,14 @@ long long mk_dual_softmax_work_floats(int B, int n0, int n1, int own_copy) {
 
 }  // extern "C"
 
-// the exact-fp32 dual softmax; KF: keyframe mode (operand 0 read through kf, mickey_hip.h: mk_dual_softmax_kf)
+// the exact-fp32 dual softmax; KF: keyframe mode (operand 0 read through kf, mickey_hip.h: mk_dual_softmax_kf).
+// lse_out (training forward, mk::ds::dual_softmax_train_fwd): the merged log2-sums go there instead of `work`, merged with the
+// dustbin read from the device pointer dustbin_dev (use_dustbin / dustbin unused)
 template <bool KF>
 static int dual_softmax_impl(const float* dsc0, const float* dsc1, const float* scr0, const float* scr1, float inv_temperature,
                              int use_dustbin, float dustbin, float* scores, float* kp_scores, float* final_scores, float* work, int B,
-                             int C, int n0, int n1, const int* kf, int K, hipStream_t st) {
+                             int C, int n0, int n1, const int* kf, int K, hipStream_t st, float* lse_out = nullptr,
+                             const float* dustbin_dev = nullptr) {
   MK_CHECK_ARG(B > 0 && n0 > 0 && n1 > 0 && C > 0 && C <= CMAX && C % 2 == 0, "mk_dual_softmax: need 0 < C <= %d, C even", CMAX);
   MK_CHECK_ARG((scr0 && scr1) || (!kp_scores && !final_scores), "mk_dual_softmax: kp/final scores need scr0 and scr1");
   const int nmax = n0 > n1 ? n0 : n1, nrb = (n0 + RT - 1) / RT;
@@ -799,6 +687,7 @@ static int dual_softmax_impl(const float* dsc0, const float* dsc1, const float* 
   float* partc = partr + (long long)B * NCHUNK * n0 * 2;
   float* lse2 = partc + (long long)B * nrb * n1 * 2;
   float* vown = lse2 + (((long long)B * 2 * nmax + 3) & ~3LL);   // 16-byte aligned when `work` is
+  if (lse_out) lse2 = lse_out;
   // in place when the caller wants `scores` or `final_scores` anyway (pass 2 reads an element, then overwrites it)
   float* vbuf = scores ? scores : final_scores ? final_scores : vown;
   const int gx1 = (n0 + 4 * RT - 1) / (4 * RT);
@@ -810,9 +699,14 @@ static int dual_softmax_impl(const float* dsc0, const float* dsc1, const float* 
     hipLaunchKernelGGL((lse_partial_kernel<false, KF>), g1, dim3(256), 0, st, dsc0, dsc1, scale2, partr, partc, vbuf, C, n0, n1, nrb, gx1, B,
                        kf, K);
   MK_CHECK_LAUNCH();
-  hipLaunchKernelGGL(lse_final_kernel, dim3((nmax + 255) / 256, 2, B), dim3(256), 0, st, partr, partc, lse2, use_dustbin,
-                     dustbin * LOG2E, n0, n1, nmax, nrb, NCHUNK);
-  MK_CHECK_LAUNCH();
+  if (lse_out) {
+    const int rc = lse_merge_dev(partr, partc, lse2, dustbin_dev, B, n0, n1, nrb, NCHUNK, st);
+    if (rc != MK_OK) return rc;
+  } else {
+    hipLaunchKernelGGL(lse_final_kernel, dim3((nmax + 255) / 256, 2, B), dim3(256), 0, st, partr, partc, lse2, use_dustbin,
+                       dustbin * LOG2E, n0, n1, nmax, nrb, NCHUNK);
+    MK_CHECK_LAUNCH();
+  }
   if (scores || kp_scores || final_scores) {
     // rows of vbuf / outputs start at multiples of n1 floats: 8-byte vectors need n1 even and 8-byte-aligned bases
     const bool v2 = (n1 % 2 == 0) && ((((uintptr_t)vbuf | (uintptr_t)scores | (uintptr_t)kp_scores | (uintptr_t)final_scores |
@@ -860,10 +754,12 @@ long long mk_dual_softmax_split_work_floats(int B, int n0, int n1) {
 
 // the split-fp16 dual softmax; KF: keyframe mode (mickey_hip.h: mk_dual_softmax_split_kf): the planes of operand 0 are made for the
 // K keyframes only (rows [0, K) of P0's B-pair region) and the passes address them through kf
+// lse_out / dustbin_dev: as for dual_softmax_impl
 template <bool KF>
 static int dual_softmax_split_impl(const float* dsc0, const float* dsc1, const float* scr0, const float* scr1, float inv_temperature,
                                    int use_dustbin, float dustbin, float* scores, float* kp_scores, float* final_scores, float* work,
-                                   int B, int C, int n0, int n1, const int* kf, int K, hipStream_t st) {
+                                   int B, int C, int n0, int n1, const int* kf, int K, hipStream_t st, float* lse_out = nullptr,
+                                   const float* dustbin_dev = nullptr) {
   MK_CHECK_ARG(B > 0 && n0 > 0 && n1 > 0 && C == 16 * SP_KS, "mk_dual_softmax_split: C must be %d (use mk_dual_softmax otherwise)", 16 * SP_KS);
   MK_CHECK_ARG((scr0 && scr1) || (!kp_scores && !final_scores), "mk_dual_softmax_split: kp/final scores need scr0 and scr1");
   MK_CHECK_ARG(((uintptr_t)work & 15) == 0, "mk_dual_softmax_split: work must be 16-byte aligned");
@@ -876,7 +772,7 @@ static int dual_softmax_split_impl(const float* dsc0, const float* dsc1, const f
   uint4* P1 = P0 + (long long)B * nrb * SP_BLK_U4;
   float* partr = (float*)(P1 + (long long)B * ntb * SP_BLK_U4);
   float* partc = partr + (long long)B * NCHUNK_S * n0 * 2;
-  float* lse2 = partc + (long long)B * nrb * n1 * 2;
+  float* lse2 = lse_out ? lse_out : partc + (long long)B * nrb * n1 * 2;
   hipLaunchKernelGGL(dsc_split_kernel, dim3(nrb, K), dim3(512), 0, st, dsc0, P0, n0, nrb);
   hipLaunchKernelGGL(dsc_split_kernel, dim3(ntb, B), dim3(512), 0, st, dsc1, P1, n1, ntb);
   MK_CHECK_LAUNCH();
@@ -885,9 +781,14 @@ static int dual_softmax_split_impl(const float* dsc0, const float* dsc1, const f
   const dim3 g((unsigned)gx * NCHUNK_S * ((B + 7) / 8 * 8));   // see decode_unit_grid
   hipLaunchKernelGGL(lse_split_kernel<KF>, g, dim3(256), 0, st, P0, P1, scale2, partr, partc, n0, n1, nrb, ntb, gx, B, kf, K);
   MK_CHECK_LAUNCH();
-  hipLaunchKernelGGL(lse_final_kernel, dim3((nmax + 255) / 256, 2, B), dim3(256), 0, st, partr, partc, lse2, use_dustbin,
-                     dustbin * LOG2E, n0, n1, nmax, nrb, NCHUNK_S);
-  MK_CHECK_LAUNCH();
+  if (lse_out) {
+    const int rc = lse_merge_dev(partr, partc, lse2, dustbin_dev, B, n0, n1, nrb, NCHUNK_S, st);
+    if (rc != MK_OK) return rc;
+  } else {
+    hipLaunchKernelGGL(lse_final_kernel, dim3((nmax + 255) / 256, 2, B), dim3(256), 0, st, partr, partc, lse2, use_dustbin,
+                       dustbin * LOG2E, n0, n1, nmax, nrb, NCHUNK_S);
+    MK_CHECK_LAUNCH();
+  }
   if (scores || kp_scores || final_scores) {
     // pass 2 is a WRITER: the fewer output rows the chip has in flight at a time, the more of its 256-byte row pieces meet open
     // DRAM pages.  g_ds_chunk2 column chunks per row block (dev knob; 0 = one pair of column tiles per wave: the smallest window)
@@ -928,6 +829,32 @@ int mk_dual_softmax_split_kf(const float* dsc0, const float* dsc1, const float* 
   return dual_softmax_split_impl<false>(dsc0, dsc1, scr0, scr1, inv_temperature, use_dustbin, dustbin, scores, kp_scores, final_scores,
                                         work, B, C, n0, n1, nullptr, B, (hipStream_t)stream);
 }
+
+}  // extern "C"
+
+namespace mk {
+namespace ds {
+
+int split_planes(const float* dsc, uint4* planes, int n, int nblk, int nimg, hipStream_t st) {
+  hipLaunchKernelGGL(dsc_split_kernel, dim3(nblk, nimg), dim3(512), 0, st, dsc, planes, n, nblk);
+  MK_CHECK_LAUNCH();
+  return MK_OK;
+}
+
+int dual_softmax_train_fwd(int split, const float* dsc0, const float* dsc1, const float* scr0, const float* scr1,
+                           float inv_temperature, const float* dustbin, float* scores, float* kp_scores, float* final_scores,
+                           float* lse, float* work, int B, int C, int n0, int n1, hipStream_t st) {
+  if (split)
+    return dual_softmax_split_impl<false>(dsc0, dsc1, scr0, scr1, inv_temperature, 0, 0.f, scores, kp_scores, final_scores, work, B,
+                                          C, n0, n1, nullptr, B, st, lse, dustbin);
+  return dual_softmax_impl<false>(dsc0, dsc1, scr0, scr1, inv_temperature, 0, 0.f, scores, kp_scores, final_scores, work, B, C, n0,
+                                  n1, nullptr, B, st, lse, dustbin);
+}
+
+}  // namespace ds
+}  // namespace mk
+
+extern "C" {
 
 static inline int sk_ldz(int n1) { return (n1 + 1 + 3) & ~3; }
 static inline int sk_ldu(int n0) { return (n0 + 1 + 3) & ~3; }

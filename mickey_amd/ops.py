@@ -410,6 +410,36 @@ def dual_softmax(dsc0, dsc1, scr0=None, scr1=None, temperature=0.1, dustbin=None
     return scores, kp, fin
 
 
+def dual_softmax_train_fwd(dsc0, dsc1, scr0, scr1, temperature, dustbin, split):
+    """mk_dual_softmax_train (the forward of mickey_amd.train_matcher.dual_softmax_train; arguments validated there) ->
+    (final_scores, or scores when scr0 / scr1 are None; lse [B, 2, max(n0, n1)], log2 domain).  dustbin: None or a one-element
+    fp32 device tensor, read on the device."""
+    B, C, n0 = dsc0.shape
+    n1 = dsc1.shape[2]
+    dev = dsc0.device
+    out = torch.empty((B, n0, n1), device=dev, dtype=torch.float32)
+    lse = torch.empty((B, 2, max(n0, n1)), device=dev, dtype=torch.float32)
+    work = torch.empty((query("mk_dual_softmax_train_work_floats", B, n0, n1, int(split)),), device=dev, dtype=torch.float32)
+    has_kp = scr0 is not None
+    call("mk_dual_softmax_train", ptr(dsc0), ptr(dsc1), ptr(scr0), ptr(scr1), 1.0 / float(temperature), ptr(dustbin),
+         None if has_kp else ptr(out), None, ptr(out) if has_kp else None, ptr(lse), ptr(work), B, C, n0, n1, int(split), stream())
+    return out, lse
+
+
+def dual_softmax_bwd(dsc0, dsc1, scr0, scr1, temperature, dustbin, lse, G, split, need):
+    """mk_dual_softmax_bwd: G = d loss / d (the output of dual_softmax_train_fwd) -> (g_dsc0, g_dsc1, g_scr0, g_scr1, g_dustbin
+    [B] per pair); need: five booleans in that order, None where not needed."""
+    B, C, n0 = dsc0.shape
+    n1 = dsc1.shape[2]
+    dev = dsc0.device
+    shapes = ((B, C, n0), (B, C, n1), (B, n0), (B, n1), (B,))
+    outs = [torch.empty(sh, device=dev, dtype=torch.float32) if want else None for sh, want in zip(shapes, need)]
+    work = torch.empty((query("mk_dual_softmax_bwd_work_floats", B, n0, n1, int(split)),), device=dev, dtype=torch.float32)
+    call("mk_dual_softmax_bwd", ptr(dsc0), ptr(dsc1), ptr(scr0), ptr(scr1), 1.0 / float(temperature), ptr(dustbin), ptr(lse),
+         ptr(G), *[ptr(o) for o in outs], ptr(work), B, C, n0, n1, int(split), stream())
+    return tuple(outs)
+
+
 def dual_softmax_set_chunks(chunks):
     """Dev knob (mickey_hip_dev.h): column chunks per row block in pass 2 of mk_dual_softmax_split (0 = default)."""
     call("mk_dual_softmax_set_chunks", int(chunks))
