@@ -378,9 +378,10 @@ int mk_mutual_nn(const float* scores, int* matches, int* count, int* work, int B
  *          mk_exprace_topk_state_bytes(B, rows_per_pair) bytes are SELF-CLEANING state (per-row candidate counts, per-pair
  *          flags and histograms, arrival counters): they must be ZERO when a call starts and every call leaves them zero, so
  *          the chain carries no zero-fill launch -- zero the buffer once when it is allocated and reuse it; a buffer must not
- *          be shared by calls that may run concurrently (two streams).  The chain is four launches: histogram of p (+ the
- *          threshold as its tail), the collect pass (+ the shortfall check as its tail), the exact fallback (idle unless a
- *          pair came up short), the select kernel.
+ *          be shared by calls that may run concurrently (two streams).  After a call that returns an error the state is
+ *          undefined (the chain may have stopped between its launches): zero those bytes again before the buffer's next use.
+ *          The chain is four launches: histogram of p (+ the threshold as its tail), the collect pass, the exact fallback
+ *          (+ the shortfall check as its head; idle unless a pair came up short), the select kernel.
  *   pair_base  GLOBAL index of pair 0 of this call.  The Philox streams are keyed by (seed, offset, global pair index,
  *          draw, cell), so a batch may be split arbitrarily -- over calls or over the GPUs of a node -- without changing
  *          any pair's draws: pair i of a B = 32 call and the same pair alone with pair_base = i sample identically. */

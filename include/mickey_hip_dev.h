@@ -30,19 +30,6 @@ int mk_gemm_set_tile(int mode);
  * 4 / 5 are each bit-identical families, the two families differ in the last bits.  Process-wide; for benchmarks and tests. */
 int mk_attn_set_mode(int mode);
 
-/* mk_dual_softmax_split, pass 2 (the writer of scores / kp_scores / final_scores): column chunks per 32-row block = waves
- * that share one block's rows; 0 = one pair of column tiles per wave (default), 8 = round 4's first version (A/B). */
-int mk_dual_softmax_set_chunks(int chunks);
-
-/* mk_sinkhorn: n > 0 = n image pairs iterated together through all Sinkhorn iterations (so that their coupling matrices could
- * stay in the 256-MB Infinity Cache between the 20 passes; measured no faster: profiles/r04c_bench_matcher.txt), 0 = the
- * whole batch per pass with non-temporal reads (default). */
-int mk_sinkhorn_set_group(int pairs);
-
-/* mk_exprace_topk, on-device draws: 0 = candidates generated by geometric skipping (default), 1 = the collect pass that
- * tests every (row, cell) behind a 6-bit pre-filter (round 3; A/B partner and statistical cross-check). */
-int mk_exprace_set_mode(int mode);
-
 /* Measurement probe (bench.py `roofline.peak_sustained`): back-to-back v_mfma_f32_16x16x32 (bf16) on register-resident operands
  * (pseudo-random, or zeros), `workgroups` x 8 waves x `iters` x 8 MFMAs = workgroups * iters * 1048576 flops per launch, no memory
  * traffic: what the socket power limit lets through the matrix pipe alone (LABNOTES R4.11).  scratch: >= workgroups * 512 floats. */

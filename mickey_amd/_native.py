@@ -85,9 +85,6 @@ SIGNATURES = {
 DEV_SIGNATURES = {
     "mk_gemm_set_tile": ("i", "i"),
     "mk_attn_set_mode": ("i", "i"),
-    "mk_sinkhorn_set_group": ("i", "i"),
-    "mk_dual_softmax_set_chunks": ("i", "i"),
-    "mk_exprace_set_mode": ("i", "i"),
     "mk_dev_mfma_sustained": ("i", "piiip"),
 }
 

@@ -425,7 +425,6 @@ __global__ __launch_bounds__(256) void couplings_kernel(const float* __restrict_
 }
 
 // u2[i] = log_mu2[i] - LSE2_j(Z2[i][j] + v2[j]); one wave per row, 16 bytes per lane
-template <bool NT>
 __global__ __launch_bounds__(256) void sink_row_kernel(const float* __restrict__ Z, const float* __restrict__ v,
                                                        float* __restrict__ u, int n0, int ldz, int ldu, float norm2, float last2) {
   const int lane = threadIdx.x & 63;
@@ -435,7 +434,7 @@ __global__ __launch_bounds__(256) void sink_row_kernel(const float* __restrict__
   const f32x4* vb = (const f32x4*)(v + (long long)b * ldz);
   float m = -1e30f, s = 0.f;
   for (int j4 = lane; j4 < (ldz >> 2); j4 += 64) {
-    const f32x4 x = (NT ? __builtin_nontemporal_load(z + j4) : z[j4]) + vb[j4];
+    const f32x4 x = __builtin_nontemporal_load(z + j4) + vb[j4];
     const float M = fmaxf(fmaxf(fmaxf(x[0], x[1]), fmaxf(x[2], x[3])), m);
     s = s * __builtin_amdgcn_exp2f(m - M) + ((__builtin_amdgcn_exp2f(x[0] - M) + __builtin_amdgcn_exp2f(x[1] - M)) +
                                              (__builtin_amdgcn_exp2f(x[2] - M) + __builtin_amdgcn_exp2f(x[3] - M)));
@@ -451,7 +450,6 @@ __global__ __launch_bounds__(256) void sink_row_kernel(const float* __restrict__
 
 // column pass, part 1: (max, sum) of 2^(Z2[i][j] + u2[i]) over the rows of one 256-row chunk for 256 columns; a wave takes 64 of
 // the rows, 8 at a time (one running-maximum update per 8 values of a column), a lane 4 adjacent columns
-template <bool NT>
 __global__ __launch_bounds__(256) void sink_col_part_kernel(const float* __restrict__ Z, const float* __restrict__ u,
                                                             float2* __restrict__ part, int n0, int ldz, int ldu, int nrc) {
   __shared__ f32x4 sm[4][64], ss[4][64];
@@ -471,7 +469,7 @@ __global__ __launch_bounds__(256) void sink_col_part_kernel(const float* __restr
       const int ic = i <= n0 ? i : n0;
       const float ui = i <= n0 ? ub[ic] : -1e30f;
       const f32x4* zp = (const f32x4*)(Zb + (long long)ic * ldz);
-      x[k] = (NT ? __builtin_nontemporal_load(zp) : *zp) + ui;
+      x[k] = __builtin_nontemporal_load(zp) + ui;
     }
     f32x4 M = m;
 #pragma unroll
@@ -655,9 +653,6 @@ __global__ __launch_bounds__(1024) void mutual_collect_kernel(const int* __restr
 
 }  // namespace
 
-static int g_ds_chunk2 = 0;   // dual softmax (split path): column chunks of pass 2 per row block (0 = one pair of tiles per wave)
-static int g_sk_group = 0;   // Sinkhorn: pairs iterated together (0: the whole batch per pass with non-temporal reads)
-
 extern "C" {
 
 long long mk_dual_softmax_work_floats(int B, int n0, int n1, int own_copy) {
@@ -791,8 +786,8 @@ static int dual_softmax_split_impl(const float* dsc0, const float* dsc1, const f
   }
   if (scores || kp_scores || final_scores) {
     // pass 2 is a WRITER: the fewer output rows the chip has in flight at a time, the more of its 256-byte row pieces meet open
-    // DRAM pages.  g_ds_chunk2 column chunks per row block (dev knob; 0 = one pair of column tiles per wave: the smallest window)
-    const int nchunk2 = g_ds_chunk2 > 0 ? g_ds_chunk2 : (ntb + 1) / 2;
+    // DRAM pages: one pair of column tiles per wave, the smallest window
+    const int nchunk2 = (ntb + 1) / 2;
     const dim3 g2((unsigned)gx * nchunk2 * ((B + 7) / 8 * 8));
     const bool a16 = ((((uintptr_t)scores | (uintptr_t)kp_scores | (uintptr_t)final_scores) & 15) == 0);
     if ((n1 & 3) == 0 && a16)
@@ -868,7 +863,7 @@ long long mk_sinkhorn_work_floats(int B, int n0, int n1) {
 
 }  // extern "C"
 
-// KF: keyframe mode (mickey_hip.h: mk_sinkhorn_kf): operand 0 (dsc0, scr0) read through kf; a pair group passes its slice of the map
+// KF: keyframe mode (mickey_hip.h: mk_sinkhorn_kf): operand 0 (dsc0, scr0) read through kf
 template <bool KF>
 static int sinkhorn_impl(const float* dsc0, const float* dsc1, const float* scr0, const float* scr1, float alpha, int iters, float* scores,
                          float* kp_scores, float* final_scores, float* work, int B, int C, int n0, int n1, const int* kf, int K,
@@ -885,48 +880,22 @@ static int sinkhorn_impl(const float* dsc0, const float* dsc1, const float* scr0
   const float LOG2E = 1.4426950408889634f;
   const float norm = -logf((float)n0 + (float)n1);
   const float norm2 = norm * LOG2E, mu_last2 = (logf((float)n1) + norm) * LOG2E, nu_last2 = (logf((float)n0) + norm) * LOG2E;
-  // The 20 LSE passes of a pair re-read its (n0+1) x ldz coupling matrix (15 MB at 540x720, 86 MB at 1280x720).  Round 4
-  // measured whether cutting the batch into groups of pairs whose matrices fit the 256-MB Infinity Cache together -- a group
-  // runs ALL its iterations before the next starts, reads without the non-temporal hint -- turns HBM passes into cache hits:
-  // it does not (8 pairs of 1280x720: 5.49 ms batch-wide, 5.64 / 5.64 / 6.09 ms in groups of 4 / 2 / 1,
-  // profiles/r04c_bench_matcher.txt).  The batch-wide order stays the default; g_sk_group > 0 (dev knob
-  // mk_sinkhorn_set_group) selects the grouped one.
-  const long long zbytes = (long long)(n0 + 1) * ldz * 4;
-  int group = g_sk_group > 0 ? g_sk_group : B;
-  if (group > B) group = B;
-  const bool nt = g_sk_group <= 0 || (long long)group * zbytes > (240LL << 20);
-  for (int b0 = 0; b0 < B; b0 += group) {
-    const int nb = group < B - b0 ? group : B - b0;
-    const float* d0 = KF ? dsc0 : dsc0 + (long long)b0 * C * n0;   // (keyframe mode: the group's map slice selects the rows)
-    const int* kg = KF ? kf + b0 : nullptr;
-    const float* d1 = dsc1 + (long long)b0 * C * n1;
-    float* Zg = Z + (long long)b0 * (n0 + 1) * ldz;
-    float* ug = u + (long long)b0 * ldu;
-    float* vg = v + (long long)b0 * ldz;
-    float2* pg = part + (long long)b0 * nrc * ldz;
-    hipLaunchKernelGGL(couplings_kernel<KF>, dim3((ldz + MT - 1) / MT, (n0 + 1 + MT - 1) / MT, nb), dim3(256), 0, st, d0, d1,
-                       LOG2E / sqrtf((float)C), alpha * LOG2E, Zg, C, n0, n1, ldz, kg, K);
-    MK_CHECK_LAUNCH();
-    hipLaunchKernelGGL(fill_kernel, dim3((unsigned)(((long long)nb * ldu + 255) / 256)), dim3(256), 0, st, ug, 0.f, (long long)nb * ldu);
-    hipLaunchKernelGGL(fill_kernel, dim3((unsigned)(((long long)nb * ldz + 255) / 256)), dim3(256), 0, st, vg, 0.f, (long long)nb * ldz);
-    MK_CHECK_LAUNCH();
-    for (int it = 0; it < iters; ++it) {
-      if (nt) {
-        hipLaunchKernelGGL(sink_row_kernel<true>, dim3((n0 + 1 + 3) / 4, nb), dim3(256), 0, st, Zg, vg, ug, n0, ldz, ldu, norm2, mu_last2);
-        hipLaunchKernelGGL(sink_col_part_kernel<true>, dim3((ldz / 4 + 63) / 64, nrc, nb), dim3(256), 0, st, Zg, ug, pg, n0, ldz, ldu, nrc);
-      } else {
-        hipLaunchKernelGGL(sink_row_kernel<false>, dim3((n0 + 1 + 3) / 4, nb), dim3(256), 0, st, Zg, vg, ug, n0, ldz, ldu, norm2, mu_last2);
-        hipLaunchKernelGGL(sink_col_part_kernel<false>, dim3((ldz / 4 + 63) / 64, nrc, nb), dim3(256), 0, st, Zg, ug, pg, n0, ldz, ldu, nrc);
-      }
-      hipLaunchKernelGGL(sink_col_fin_kernel, dim3((ldz + 255) / 256, nb), dim3(256), 0, st, pg, vg, n1, ldz, nrc, norm2, nu_last2);
-    }
-    MK_CHECK_LAUNCH();
-    hipLaunchKernelGGL(sink_final_kernel<KF>, dim3((n1 + 255) / 256, n0, nb), dim3(256), 0, st, Zg, ug, vg, norm2,
-                       scr0 ? (KF ? scr0 : scr0 + (long long)b0 * n0) : nullptr, scr1 ? scr1 + (long long)b0 * n1 : nullptr,
-                       scores ? scores + (long long)b0 * n0 * n1 : nullptr, kp_scores ? kp_scores + (long long)b0 * n0 * n1 : nullptr,
-                       final_scores ? final_scores + (long long)b0 * n0 * n1 : nullptr, n0, n1, ldz, ldu, kg, K);
-    MK_CHECK_LAUNCH();
+  // batch-wide passes, non-temporal reads: cache-sized groups of pairs measured no faster (profiles/r04c_bench_matcher.txt)
+  hipLaunchKernelGGL(couplings_kernel<KF>, dim3((ldz + MT - 1) / MT, (n0 + 1 + MT - 1) / MT, B), dim3(256), 0, st, dsc0, dsc1,
+                     LOG2E / sqrtf((float)C), alpha * LOG2E, Z, C, n0, n1, ldz, kf, K);
+  MK_CHECK_LAUNCH();
+  hipLaunchKernelGGL(fill_kernel, dim3((unsigned)(((long long)B * ldu + 255) / 256)), dim3(256), 0, st, u, 0.f, (long long)B * ldu);
+  hipLaunchKernelGGL(fill_kernel, dim3((unsigned)(((long long)B * ldz + 255) / 256)), dim3(256), 0, st, v, 0.f, (long long)B * ldz);
+  MK_CHECK_LAUNCH();
+  for (int it = 0; it < iters; ++it) {
+    hipLaunchKernelGGL(sink_row_kernel, dim3((n0 + 1 + 3) / 4, B), dim3(256), 0, st, Z, v, u, n0, ldz, ldu, norm2, mu_last2);
+    hipLaunchKernelGGL(sink_col_part_kernel, dim3((ldz / 4 + 63) / 64, nrc, B), dim3(256), 0, st, Z, u, part, n0, ldz, ldu, nrc);
+    hipLaunchKernelGGL(sink_col_fin_kernel, dim3((ldz + 255) / 256, B), dim3(256), 0, st, part, v, n1, ldz, nrc, norm2, nu_last2);
   }
+  MK_CHECK_LAUNCH();
+  hipLaunchKernelGGL(sink_final_kernel<KF>, dim3((n1 + 255) / 256, n0, B), dim3(256), 0, st, Z, u, v, norm2, scr0, scr1, scores,
+                     kp_scores, final_scores, n0, n1, ldz, ldu, kf, K);
+  MK_CHECK_LAUNCH();
   return MK_OK;
 }
 
@@ -947,16 +916,6 @@ int mk_sinkhorn_kf(const float* dsc0, const float* dsc1, const float* scr0, cons
                                (hipStream_t)stream);
   return sinkhorn_impl<false>(dsc0, dsc1, scr0, scr1, alpha, iters, scores, kp_scores, final_scores, work, B, C, n0, n1, nullptr, B,
                               (hipStream_t)stream);
-}
-
-int mk_dual_softmax_set_chunks(int chunks) {
-  g_ds_chunk2 = chunks;
-  return MK_OK;
-}
-
-int mk_sinkhorn_set_group(int pairs) {
-  g_sk_group = pairs;
-  return MK_OK;
 }
 
 int mk_mutual_nn(const float* scores, int* matches, int* count, int* work, int B, int n0, int n1, mk_stream_t stream) {

@@ -10,8 +10,8 @@
 //     Exp(1) conditioned on clearing T: the law of drawing every e, RNG work proportional to the ~2600 candidates of a row
 //     instead of its 3.76 M cells); small in-LDS bitonic sort -> the same "top-k of p / Exp(1)" selection, in the same
 //     (descending key) order torch.topk returns; an exact radix-histogram path takes over on device if a row collected too
-//     few / too many.  Injected noise (tests): every (row, cell) is keyed, one streamed read per group of 4 rows.  The
-//     round-3 generator (every cell tested behind a 6-bit pre-filter) is kept as the A/B partner (mk_exprace_set_mode).
+//     few / too many.  Injected noise (tests) and more than SK_MAXROWS rows per pair: every (row, cell) is keyed, one
+//     streamed read per group of 4 rows.
 //   * mk_train_ransac_masks / mk_reinforce_scatter: the training-time RANSAC of loss/loss_class.py (8-point hypotheses,
 //     refinement of every hypothesis, REINFORCE bookkeeping).
 //   * mk_ransac_hypotheses: a correspondence set (X, Y, w: 56 KB) is staged once in LDS and shared by
@@ -73,8 +73,9 @@ constexpr int NBINS = 2048;     // bits 30..20 of a positive float: exponent + 3
 constexpr int RG = 4;           // rows per group = draws per Philox call
 constexpr int CAND_MAX = 8192;  // candidates kept per row (expected ~k * 1.1)
 constexpr int CELL_BLOCKS = 128;
+constexpr unsigned FCNT_REDONE = 0x80000000u;   // (counts stay below ncell < 2^31)
 
-// Workspace of mk_exprace_topk.  The words of `ncand | redo | phist | done1` are SELF-CLEANING state: they must be zero
+// Workspace of mk_exprace_topk.  The words of `ncand | redo | phist | done1 | fcnt` are SELF-CLEANING state: they must be zero
 // when a call starts and every call leaves them zero (each is reset by its last reader), so that no zero-fill launch stands in
 // front of the chain -- mickey_hip.h: the caller zero-initialises the buffer once and never shares it between streams.
 struct TopkWork {
@@ -84,6 +85,7 @@ struct TopkWork {
                              //     (the others keep their skip-sampler draws: a pair's result never depends on its batch)
   unsigned* phist;           // [B][NBINS]   (state) histogram of p itself (analytic threshold); reset by its pair's last workgroup
   unsigned* done1;           // [B]          (state) workgroups of the histogram pass that have finished, per pair
+  unsigned* fcnt;            // [R]          (state) FCNT_REDONE | candidates of a row the exact fallback redid; reset by the select kernel
   int* thr;                  // [R]
   unsigned long long* cand;  // [R][CAND_MAX]
   int* invalid;              // [1] or null
@@ -115,7 +117,7 @@ __device__ __forceinline__ void row_keys(const float* __restrict__ noise, unsign
 // round trip whenever any of its 256 keys is a candidate -- inside the Philox loop that was ~25 % of the pass.
 constexpr int LCAP = 960;   // LDS candidate slots per row and block (expected ~25 at k = 2048, 128 blocks); overflow goes direct
 
-// (the every-cell collect pass: injected noise -- tests -- and more rows per pair than the generators below are built for)
+// (the every-cell collect pass: injected noise -- tests -- and more rows per pair than the skip sampler below is built for)
 __global__ __launch_bounds__(256) void exprace_scan_kernel(const float* __restrict__ p, const float* __restrict__ noise,
                                                            unsigned k0, unsigned k1, unsigned off_lo, unsigned off_hi,
                                                            const unsigned long long* __restrict__ offp, TopkWork w,
@@ -194,7 +196,8 @@ __global__ __launch_bounds__(1024) void exprace_fallback_kernel(const float* __r
   // does this pair need the fallback?  A queue of the generator overflowed (`redo`, raised there), or one of the pair's rows fell
   // short of k candidates although its threshold was not "everything", or overflowed its candidate buffer (noise that is not
   // Exp(1)-distributed can do either).  Every workgroup of the pair evaluates the same rows_per_pair counts: no hand-over between
-  // workgroups, no check launch, no tail in the collect pass (round 6).
+  // workgroups, no check launch, no tail in the collect pass (round 6).  No workgroup of this kernel writes the words read here
+  // (its counts go to `fcnt`), so every workgroup of the pair decides the same way, in any schedule.
   __shared__ int need_s;
   if (t == 0) need_s = w.redo[b];
   __syncthreads();
@@ -243,7 +246,6 @@ __global__ __launch_bounds__(1024) void exprace_fallback_kernel(const float* __r
         run += part[s8];
       }
       thr_s[q] = tb;
-      if (grp * RG + q < rows_per_pair) w.thr[b * rows_per_pair + grp * RG + q] = tb;
     }
     __syncthreads();
   }
@@ -264,134 +266,13 @@ __global__ __launch_bounds__(1024) void exprace_fallback_kernel(const float* __r
     }
   }
   __syncthreads();
-  if (t < RG && grp * RG + t < rows_per_pair) w.ncand[b * rows_per_pair + grp * RG + t] = cnt_s[t];   // replaces what the generator counted
-}
-
-// ---- Philox collect pass with a 6-bit pre-filter ---------------------------------------------------------------------
-// The scan above draws one full uniform per (row, cell): 5 Philox calls per cell for 20 rows, 2.4 G draws per 32-pair
-// step, of which one in ~1400 becomes a candidate.  A key p/e reaches the threshold T only if e = -ln(u) <= p/T; for a
-// cell with p < 0.0155 T that needs u > 1 - 2^-6, i.e. the top 6 bits of the 24-bit uniform all ones.  So:
-//   stage 1  one Philox call per cell yields the TOP 6 bits of the uniforms of 20 rows (5 x 6 bits per 32-bit word); only
-//            (cell, row) pairs whose 6 bits are all ones (1 in 64) are queued in LDS;
-//   stage 2  the queue is processed densely: one Philox call per queued pair, keyed by (cell, row), yields the LOW 18
-//            bits; u = (top6 << 18 | low18 + 0.5) 2^-24, key = p / -ln(u), candidate test, append (as in the scan).
-// The joint distribution is that of independent 24-bit uniforms per (row, cell) -- the sampler is unchanged, the RNG work
-// drops from 5 to ~1.3 Philox calls per cell.  Cells with p >= 0.0155 T (a few thousand per pair) take stage 2 for all
-// their rows.  Counter layout: z = (pair + pair_base) * 512 + {256 + row / 20 (stage 1) | row (stage 2)}.
-constexpr int PF_CPT = 3;         // cells per thread per iteration: 768 cells queue ~240 (cell, row) pairs = ONE dense round of stage 2
-                                  // (4 cells: 320 pairs = two rounds, the second a quarter full)
-constexpr int PF_QCAP = 2048;     // queued (cell, row) pairs per iteration (expected 320 + 20 per large-p cell)
-constexpr int PF_LCAP = 128;      // LDS candidate slots per row and block (expected ~20)
-constexpr int PF_MAXROWS = 48;   // LDS: rows x 1 KiB of candidates + 8 KiB queue <= 56 KiB
-
-__global__ __launch_bounds__(256) void exprace_prefilter_kernel(const float* __restrict__ p, unsigned k0, unsigned k1,
-                                                                unsigned off_lo, unsigned off_hi,
-                                                                const unsigned long long* __restrict__ offp, TopkWork w,
-                                                                int rows_per_pair, long long ncell) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char pf_smem[];
-  unsigned long long* lbuf = (unsigned long long*)pf_smem;                       // [rows][PF_LCAP]
-  unsigned* queue = (unsigned*)(pf_smem + (size_t)rows_per_pair * PF_LCAP * 8);   // [PF_QCAP]
-  __shared__ unsigned lcount[PF_MAXROWS], lbase[PF_MAXROWS];
-  __shared__ unsigned qcount;
-  add_device_offset(off_lo, off_hi, offp);
-  const int b = blockIdx.y;
-  const long long per = (ncell + gridDim.x - 1) / gridDim.x;
-  const long long c0 = blockIdx.x * per, c1 = min(ncell, c0 + per);
-  const unsigned zb = (unsigned)(b + w.pair_base) * 512u;
-  const int thr0 = w.thr[b * rows_per_pair];          // one analytic threshold per pair (the tail of exprace_phist_kernel)
-  const float T = __uint_as_float((unsigned)thr0 << 20);
-  const float pfast = 0.0155f * T;                     // -ln(1 - 2^-6) = 0.015748: margin for the 1-ulp log / rcp
-  const float pnever = 2.9e-8f * T;                    // smallest e: -ln(1 - 2^-25) = 2.98e-8
-  if (threadIdx.x < rows_per_pair) lcount[threadIdx.x] = 0;
-  if (threadIdx.x == 0) qcount = 0;
-  __syncthreads();
-  const float* pb = p + (long long)b * ncell;
-
-  auto finish = [&](unsigned cl, int r, unsigned top6) {   // stage 2 for one (cell, row)
-    const long long c = c0 + cl;
-    const float pv = pb[c];
-    const U4 rnd = philox4x32(k0, k1, U4{(unsigned)c, off_hi, zb + (unsigned)r, off_lo});
-    const unsigned r24 = (top6 << 18) | (rnd.x >> 14);
-    const float key = race_key(pv, r24 << 8);
-    const unsigned bits = __float_as_uint(key);
-    if ((int)((bits & 0x7fffffffu) >> 20) < thr0) return;
-    const unsigned long long item = ((unsigned long long)bits << 32) | (unsigned)(0xffffffffu - (unsigned)c);
-    const unsigned ls = atomicAdd(&lcount[r], 1u);
-    if (ls < (unsigned)PF_LCAP) {
-      lbuf[r * PF_LCAP + ls] = item;
-    } else {
-      const int row = b * rows_per_pair + r;
-      const unsigned slot = atomicAdd(&w.ncand[row], 1u);
-      if (slot < CAND_MAX) w.cand[(long long)row * CAND_MAX + slot] = item;
-    }
-  };
-
-  for (long long base = c0; base < c1; base += 256 * PF_CPT) {
-#pragma unroll
-    for (int u = 0; u < PF_CPT; ++u) {
-      const long long c = base + u * 256 + threadIdx.x;
-      if (c >= c1) continue;
-      const float pv = pb[c];
-      if (!(pv > pnever) || isinf(pv)) continue;   // key <= p / e_min < T for every possible draw (and p <= 0)
-      const unsigned cl = (unsigned)(c - c0);
-      const bool fast = pv < pfast;
-      for (int rc = 0; rc * 20 < rows_per_pair; ++rc) {
-        const U4 rnd = philox4x32(k0, k1, U4{(unsigned)c, off_hi, zb + 256u + (unsigned)rc, off_lo});
-        const unsigned wd[4] = {rnd.x, rnd.y, rnd.z, rnd.w};
-        // 20-bit mask of the rows to queue: all of them for a large-p cell, otherwise those whose 6-bit field is all ones
-        // (bit 0 of each field of ~x OR-folded over the field is 0 exactly then) -- ~12 ops per word instead of a
-        // compare + branch per row
-        unsigned mask = 0;
-#pragma unroll
-        for (int v = 0; v < 4; ++v) {
-          const unsigned y = ~wd[v];
-          const unsigned z = (y | (y >> 1) | (y >> 2) | (y >> 3) | (y >> 4) | (y >> 5)) & 0x01041041u;   // 1 = field not all ones
-          const unsigned pass = ~z & 0x01041041u;
-          const unsigned m5 = (pass & 1u) | ((pass >> 5) & 2u) | ((pass >> 10) & 4u) | ((pass >> 15) & 8u) | ((pass >> 20) & 16u);
-          mask |= m5 << (5 * v);
-        }
-        const int nr = min(20, rows_per_pair - rc * 20);
-        if (!fast) mask = 0xfffffu;
-        mask &= (1u << nr) - 1u;
-        while (mask) {
-          const int q = __builtin_ctz(mask);
-          mask &= mask - 1u;
-          const unsigned top6 = (wd[q / 5] >> (6 * (q % 5))) & 63u;
-          const int r = rc * 20 + q;
-          const unsigned pos = atomicAdd(&qcount, 1u);
-          if (pos < (unsigned)PF_QCAP) queue[pos] = cl | ((unsigned)r << 16) | (top6 << 24);
-          else finish(cl, r, top6);   // queue full (many large-p cells in one iteration): do it in place
-        }
-      }
-    }
-    __syncthreads();
-    const unsigned n = min(qcount, (unsigned)PF_QCAP);
-    for (unsigned i = threadIdx.x; i < n; i += 256) {
-      const unsigned it = queue[i];
-      finish(it & 0xffffu, (int)((it >> 16) & 0xffu), it >> 24);
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) qcount = 0;
-    __syncthreads();
-  }
-  if (threadIdx.x < rows_per_pair) {
-    const int r = threadIdx.x;
-    const unsigned nloc = min(lcount[r], (unsigned)PF_LCAP);
-    lbase[r] = nloc ? atomicAdd(&w.ncand[b * rows_per_pair + r], nloc) : 0u;
-  }
-  __syncthreads();
-  for (int r = 0; r < rows_per_pair; ++r) {
-    const unsigned nloc = min(lcount[r], (unsigned)PF_LCAP), bs = lbase[r];
-    const long long row = (long long)b * rows_per_pair + r;
-    for (unsigned i = threadIdx.x; i < nloc; i += 256)
-      if (bs + i < (unsigned)CAND_MAX) w.cand[row * CAND_MAX + bs + i] = lbuf[r * PF_LCAP + i];
-  }
+  if (t < RG && grp * RG + t < rows_per_pair) w.fcnt[b * rows_per_pair + grp * RG + t] = FCNT_REDONE | cnt_s[t];   // replaces ncand
 }
 
 // ---- Philox collect pass by geometric skipping (the product path) ------------------------------------------------------------
 // With the analytic threshold T a (row, cell) becomes a candidate iff its Exp(1) draw e < p / T: independent Bernoulli events
 // of probability s = 1 - exp(-p / T), ~7e-4 on average (1.25 k candidates per row out of n^2 cells).  Testing every (row, cell)
-// costs a Philox call per cell even with the pre-filter above; here the candidates of a row are generated DIRECTLY, as a thinned
+// costs a Philox call per cell (the scan pass above); here the candidates of a row are generated DIRECTLY, as a thinned
 // Bernoulli process:
 //   bound     pmax = largest p of every 16 consecutive cells (written by the histogram pass): every cell of the block is
 //             "proposed" with probability S = 1 - exp(-lam), lam = pmax / T >= p / T;
@@ -404,11 +285,12 @@ __global__ __launch_bounds__(256) void exprace_prefilter_kernel(const float* __r
 //             e = -log1p(-u s);
 //   dense     blocks with lam > 0.1 (around a dominant cell; everything when T = 0) skip the skipping: their 16 cells are
 //             tested directly with probability s.
-// Proposals are queued in LDS and tested densely (all lanes busy), candidates are appended as in the passes above, and the
+// Proposals are queued in LDS and tested densely (all lanes busy), candidates are appended as in the scan pass, and the
 // select kernel sorts them: the result is the top-k of the race keys of a row -- the same sampling law, with the RNG work
 // proportional to the number of candidates instead of the number of cells.  The walk geometry depends on ncell only (not on
 // the batch), so a pair's draws do not depend on the batch it is in.
 // Counter layout: x = walk thread (+ call << 26) | cell, z = (pair + pair_base) * 512 + {288 + row group (walk) | row (test)}.
+constexpr int SK_MAXROWS = 48;               // rows per pair the skip sampler takes (more: the scan pass)
 constexpr int SK_CELLS = 16;                 // cells per bound block
 constexpr int SK_NBW = 16;                   // blocks per thread (their rates live in registers for all rows of the workgroup)
 constexpr int SK_RANGE = 256 * SK_NBW;       // blocks per workgroup (65536 cells: a queue entry holds the local cell in 16 bits)
@@ -816,7 +698,8 @@ __global__ __launch_bounds__(SEL_T) void exprace_select_kernel(const float* __re
                                                                int k) {
   extern __shared__ __attribute__((aligned(16))) unsigned long long keys[];   // [SEL_LDS]
   const int row = blockIdx.x;
-  const unsigned nc_raw = w.ncand[row];
+  const unsigned f = w.fcnt[row];
+  const unsigned nc_raw = (f & FCNT_REDONE) ? f & ~FCNT_REDONE : w.ncand[row];
   const int nc = (int)min(nc_raw, (unsigned)CAND_MAX);
   int np2 = SEL_T;                   // at least one slot per thread (E = 1); CAND_MAX = 8192 -> E <= 8
   while (np2 < nc) np2 <<= 1;
@@ -838,10 +721,11 @@ __global__ __launch_bounds__(SEL_T) void exprace_select_kernel(const float* __re
       for (; f < k; ++f) idx[(long long)row * k + f] = 0;
     }
   }
-  // self-cleaning state (TopkWork): this workgroup was the last reader of its row's count, the chain's last kernel of the pair's `redo`
+  // self-cleaning state (TopkWork): this workgroup was the last reader of its row's counts, the chain's last kernel of the pair's `redo`
   __syncthreads();
   if (threadIdx.x == 0) {
     w.ncand[row] = 0;
+    w.fcnt[row] = 0;
     if (row % rows_per_pair == 0) w.redo[row / rows_per_pair] = 0;
   }
 }
@@ -1528,10 +1412,8 @@ __global__ void finalize_kernel(float* R, float* t, float* conf, const int* inva
   if (i < B) conf[i] = 0.f;
 }
 
-int g_exprace_mode = 0;   // dev (mk_exprace_set_mode): 0 = skip sampler, 1 = the 6-bit pre-filter pass
-
 // bytes of the self-cleaning state at the head of the workspace (TopkWork)
-long long topk_state_bytes(long long R, long long B) { return (R * 4 + B * 4 + B * NBINS * 4 + B * 4 + 15) / 16 * 16; }
+long long topk_state_bytes(long long R, long long B) { return (R * 4 + B * 4 + B * NBINS * 4 + B * 4 + R * 4 + 15) / 16 * 16; }
 
 TopkWork carve(void* work, int R, int B, long long ncell) {
   TopkWork w;
@@ -1540,6 +1422,7 @@ TopkWork carve(void* work, int R, int B, long long ncell) {
   w.redo = (int*)p;       p += (size_t)B * 4;
   w.phist = (unsigned*)p; p += (size_t)B * NBINS * 4;
   w.done1 = (unsigned*)p; p += (size_t)B * 4;
+  w.fcnt = (unsigned*)p;  p += (size_t)R * 4;
   p = (char*)work + topk_state_bytes(R, B);
   w.thr = (int*)p;        p += ((size_t)R * 4 + 15) / 16 * 16;
   w.cand = (unsigned long long*)p;  p += (size_t)R * CAND_MAX * 8;
@@ -1558,11 +1441,6 @@ long long mk_exprace_topk_work_bytes(int B, int rows_per_pair, int k, long long 
   return topk_state_bytes(R, B) + (R * 4 + 15) / 16 * 16 + R * CAND_MAX * 8 + (long long)B * ((ncell + SK_CELLS - 1) / SK_CELLS) * 4;
 }
 long long mk_exprace_topk_state_bytes(int B, int rows_per_pair) { return topk_state_bytes((long long)B * rows_per_pair, B); }
-int mk_exprace_set_mode(int mode) {
-  MK_CHECK_ARG(mode == 0 || mode == 1, "mk_exprace_set_mode: 0 (skip sampler) or 1 (pre-filter pass)");
-  g_exprace_mode = mode;
-  return MK_OK;
-}
 
 int mk_counter_add(unsigned long long* counter, unsigned long long inc, mk_stream_t stream) {
   MK_CHECK_ARG(counter, "mk_counter_add: null pointer");
@@ -1597,21 +1475,12 @@ int mk_exprace_topk(const float* p, const float* noise, unsigned long long seed,
   // came up short) -> select.  No zero-fill: the state words clean themselves (TopkWork).
   hipLaunchKernelGGL(exprace_phist_kernel, dim3(cb, B), dim3(256), 0, st, p, w, ncell, rows_per_pair, 1.25f * (float)k);
   MK_CHECK_LAUNCH();
-  // the block-local cell index must fit 16 bits of a queue entry: more cell blocks for very large matrices
-  int pcb = cb;
-  while ((ncell + pcb - 1) / pcb > 65536) pcb *= 2;
-  if (!noise && rows_per_pair <= PF_MAXROWS && g_exprace_mode == 0) {
+  if (!noise && rows_per_pair <= SK_MAXROWS) {
     // (the walk geometry is a function of ncell alone: a pair's draws do not depend on the batch)
     hipLaunchKernelGGL(exprace_skip_kernel, dim3((unsigned)((w.nblk + SK_RANGE - 1) / SK_RANGE), (rows_per_pair + SK_ROWS - 1) / SK_ROWS, B),
                        dim3(256), 0, st, p, k0, k1, ol, oh, offset_dev, w, rows_per_pair, ncell);
   } else {
-    if (!noise && rows_per_pair <= PF_MAXROWS) {
-      const size_t lds = (size_t)rows_per_pair * PF_LCAP * 8 + (size_t)PF_QCAP * 4;
-      hipLaunchKernelGGL(exprace_prefilter_kernel, dim3(pcb, B), dim3(256), lds, st, p, k0, k1, ol, oh, offset_dev, w, rows_per_pair,
-                         ncell);
-    } else {
-      hipLaunchKernelGGL(exprace_scan_kernel, dim3(cb, groups, B), dim3(256), 0, st, p, noise, k0, k1, ol, oh, offset_dev, w, rows_per_pair, ncell);
-    }
+    hipLaunchKernelGGL(exprace_scan_kernel, dim3(cb, groups, B), dim3(256), 0, st, p, noise, k0, k1, ol, oh, offset_dev, w, rows_per_pair, ncell);
   }
   MK_CHECK_LAUNCH();
   // exact fallback (runs only if a row came up short: never observed on a matcher's output, kept for adversarial inputs / injected noise)

@@ -440,16 +440,6 @@ def dual_softmax_bwd(dsc0, dsc1, scr0, scr1, temperature, dustbin, lse, G, split
     return tuple(outs)
 
 
-def dual_softmax_set_chunks(chunks):
-    """Dev knob (mickey_hip_dev.h): column chunks per row block in pass 2 of mk_dual_softmax_split (0 = default)."""
-    call("mk_dual_softmax_set_chunks", int(chunks))
-
-
-def sinkhorn_set_group(pairs):
-    """Dev knob (mickey_hip_dev.h): pairs iterated together by mk_sinkhorn (0 = batch-wide, non-temporal reads: default)."""
-    call("mk_sinkhorn_set_group", int(pairs))
-
-
 def sinkhorn(dsc0, dsc1, alpha, iters=10, scr0=None, scr1=None, want_scores=True, want_kp=False, want_final=False,
              keyframe_index=None):
     """Returns scores, or (scores, kp_scores, final_scores) when scr0/scr1 are given.  keyframe_index: as in dual_softmax
@@ -490,11 +480,6 @@ def counter_add(counter, inc):
     call("mk_counter_add", ptr(counter), int(inc), stream())
 
 
-def exprace_set_mode(mode):
-    """Dev knob (mickey_hip_dev.h): 0 = skip sampler (default), 1 = the pre-filter collect pass."""
-    call("mk_exprace_set_mode", int(mode))
-
-
 def dev_mfma_sustained(device, iters=400000, zero_operands=False, workgroups=None):
     """Measurement probe (mickey_hip_dev.h: mk_dev_mfma_sustained): TFLOP/s of back-to-back v_mfma_f32_16x16x32 (bf16) on
     register-resident operands, one 8-wave workgroup per CU, one warm launch + one timed launch (HIP events).  Not product code."""
@@ -519,7 +504,8 @@ def exprace_work(B, rows_per_pair, k, ncell, device):
 
 def exprace_topk(p, rows_per_pair, k, noise=None, seed=0, offset=0, invalid=None, offset_dev=None, pair_base=0, work=None):
     """p fp32 [B, ncell] -> (idx int32 [B*rows_per_pair, k], cnt int32 [B*rows_per_pair]).  work: exprace_work(...) kept by the
-    caller across calls (None: allocated and zeroed here -- one more launch)."""
+    caller across calls (None: allocated and zeroed here -- one more launch).  A call that raises zeroes the state of `work`
+    before the error propagates: the chain may have stopped between its launches (mickey_hip.h)."""
     p, noise = _c(p, noise)
     _chk(p, torch.float32)
     B, ncell = p.shape
@@ -529,8 +515,12 @@ def exprace_topk(p, rows_per_pair, k, noise=None, seed=0, offset=0, invalid=None
     if work is None:
         work = exprace_work(B, rows_per_pair, k, ncell, dev)
     assert work.numel() >= query("mk_exprace_topk_work_bytes", B, rows_per_pair, k, ncell)
-    call("mk_exprace_topk", ptr(p), ptr(noise), int(seed), int(offset), ptr(offset_dev), ptr(idx), ptr(cnt), ptr(invalid), ptr(work),
-         B, rows_per_pair, ncell, k, int(pair_base), stream())
+    try:
+        call("mk_exprace_topk", ptr(p), ptr(noise), int(seed), int(offset), ptr(offset_dev), ptr(idx), ptr(cnt), ptr(invalid),
+             ptr(work), B, rows_per_pair, ncell, k, int(pair_base), stream())
+    except Exception:
+        work[:query("mk_exprace_topk_state_bytes", B, rows_per_pair)].zero_()
+        raise
     return idx, cnt
 
 

@@ -1177,11 +1177,6 @@ def test_dual_softmax_other_shapes(B, C, n0, n1, split):
     assert rel(sc, ref) < 1e-5, rel(sc, ref)
     assert torch.equal(kp.cpu(), kp_ref)
     assert rel(fin, ref * kp_ref) < 1e-5
-    if split:   # the dev knob of pass 2 (column chunks per row block) changes the schedule, not a bit of the result
-        ops.dual_softmax_set_chunks(3)
-        sc2, kp2, fin2 = ops.dual_softmax(d0.to(dev), d1.to(dev), s0.to(dev), s1.to(dev), 0.1, 1.0, split=True)
-        ops.dual_softmax_set_chunks(0)
-        assert torch.equal(sc2, sc) and torch.equal(fin2, fin) and torch.equal(kp2, kp)
 
 
 def test_matcher_golden(golden):

@@ -94,7 +94,7 @@ def test_sampler_exact_fallback(scale):
     _assert_same_sample(idx, ref, keys)
 
 
-def test_sampler_philox_properties(sampler_mode):
+def test_sampler_philox_properties():
     from mickey_amd import ops
     dev = _dev()
     data, _, _ = _problem(B=2)
@@ -122,18 +122,8 @@ def test_sampler_philox_properties(sampler_mode):
     assert first > second
 
 
-@pytest.fixture(params=[0, 1], ids=["skip_sampler", "prefilter_pass"])
-def sampler_mode(request):
-    """Both on-device generators of the race (mk_exprace_set_mode): the product path (candidates by geometric skipping) and the
-    pass that tests every (row, cell) behind a 6-bit pre-filter."""
-    from mickey_amd import ops
-    ops.exprace_set_mode(request.param)
-    yield request.param
-    ops.exprace_set_mode(0)
-
-
-def test_sampler_many_rows_and_frequencies(sampler_mode):
-    """On-device draws, 40 rows per pair (several row groups of either generator): inclusion frequencies of a skewed 4096-cell
+def test_sampler_many_rows_and_frequencies():
+    """On-device draws, 40 rows per pair (several row groups of the skip sampler): inclusion frequencies of a skewed 4096-cell
     problem over 40 rows x 30 calls must match torch.multinomial's (two-sample chi-square), and every row is a valid draw.
     (k / ncell = 6 %: the skip sampler takes its dense branch for most blocks here; the 10 000-cell test in
     test_bench_config_gpu.py and the one below run its skipping branch.)"""
@@ -142,7 +132,7 @@ def test_sampler_many_rows_and_frequencies(sampler_mode):
     g = torch.Generator().manual_seed(11)
     ncell, k, rows = 4096, 256, 40
     p = (torch.rand(1, ncell, generator=g) ** 6 + 1e-4)
-    p[0, :50] += 3.0                       # a few dominant cells (they take the "large p" path: every row queued)
+    p[0, :50] += 3.0                       # a few dominant cells (their blocks are tested densely)
     f_hip = torch.zeros(ncell, dtype=torch.float64)
     for call in range(30):
         idx, cnt = ops.exprace_topk(p.to(dev), rows, k, seed=3, offset=call)
@@ -159,10 +149,10 @@ def test_sampler_many_rows_and_frequencies(sampler_mode):
     assert chi2 < dof + 6 * (2 * dof) ** 0.5, (chi2, dof)
 
 
-def test_sampler_first_draw_is_categorical_and_sparse_frequencies(sampler_mode):
+def test_sampler_first_draw_is_categorical_and_sparse_frequencies():
     """(a) The first index of a row is the arg-max of the race keys = ONE categorical draw ~ p (what torch.multinomial draws
     first): one-sample chi-square of 61 440 first draws against p / sum(p).  This pins the law of the race KEYS the on-device
-    generators produce (the skip sampler draws them from Exp(1) conditioned on the key clearing the threshold), not only which
+    generator produces (the skip sampler draws them from Exp(1) conditioned on the key clearing the threshold), not only which
     cells are included.  (b) 65 536 cells, k = 256 (inclusion ~4e-3: the skipping branch, several workgroup ranges, a few
     dominant cells that turn their blocks dense): two-sample chi-square of the inclusion counts against torch.multinomial."""
     from mickey_amd import ops
@@ -294,7 +284,58 @@ def test_sampler_overflow_of_one_pair_leaves_the_others_alone():
     assert bool((srt[:, 1:] != srt[:, :-1]).all())
 
 
-def test_sampler_degenerate_inputs(sampler_mode):
+def test_sampler_fallback_decision_does_not_depend_on_the_schedule():
+    """Short rows are the rule here: near-flat p, k = 16 while the analytic threshold aims at 20 candidates per row, so almost
+    every pair has a row below k and takes the exact fallback -- 512 pairs x 5 row groups of its 1024-thread workgroups, far
+    more than the chip holds at once.  Whether a pair is redone must be decided the same way by all its workgroups in any
+    order: two identical calls agree, and pairs of the batch (the last ones included) equal the same pair run alone with
+    pair_base = its index."""
+    from mickey_amd import ops
+    dev = _dev()
+    ncell, k, rows, B = 3000, 16, 20, 512
+    p = torch.rand(ncell, generator=torch.Generator().manual_seed(17)) * 0.5 + 0.5
+    pd = p.to(dev)[None].repeat(B, 1).contiguous()
+    a, ca = ops.exprace_topk(pd, rows, k, seed=5, offset=3)
+    b, cb = ops.exprace_topk(pd, rows, k, seed=5, offset=3)
+    assert torch.equal(a, b) and torch.equal(ca, cb)
+    assert int(ca.min()) == k
+    srt = a.long().sort(dim=1).values
+    assert bool((srt[:, 1:] != srt[:, :-1]).all())
+    a = a.reshape(B, rows, k)
+    for pair in (0, 1, 97, 300, B - 3, B - 2, B - 1):
+        alone, _ = ops.exprace_topk(pd[pair:pair + 1], rows, k, seed=5, offset=3, pair_base=pair)
+        assert torch.equal(alone, a[pair]), pair
+
+
+def test_sampler_failed_call_leaves_a_clean_workspace(monkeypatch):
+    """A call that raises may have stopped between the chain's launches and left state words behind: the wrapper zeroes the
+    state of the caller's buffer before the error propagates, so the next call on the same buffer equals one on a fresh buffer."""
+    from mickey_amd import ops
+    from mickey_amd._native import MickeyHipError, query
+    dev = _dev()
+    ncell, k, rows, B = 65536, 256, 20, 4
+    p = ((torch.rand((B, ncell), generator=torch.Generator().manual_seed(3)) + 0.5) * 1e-5).to(dev)
+    work = ops.exprace_work(B, rows, k, ncell, dev)
+    nstate = query("mk_exprace_topk_state_bytes", B, rows)
+    real_call = ops.call
+
+    def failing_call(name, *args):
+        if name == "mk_exprace_topk":
+            work[:nstate].fill_(0x5A)   # counts, flags and histograms of a chain that stopped half-way
+            raise MickeyHipError("mk_exprace_topk failed (injected)")
+        return real_call(name, *args)
+
+    monkeypatch.setattr(ops, "call", failing_call)
+    with pytest.raises(MickeyHipError, match="injected"):
+        ops.exprace_topk(p, rows, k, seed=4, offset=1, work=work)
+    monkeypatch.undo()
+    assert int(work[:nstate].count_nonzero()) == 0
+    got = ops.exprace_topk(p, rows, k, seed=4, offset=1, work=work)
+    ref = ops.exprace_topk(p, rows, k, seed=4, offset=1)
+    assert torch.equal(got[0], ref[0]) and torch.equal(got[1], ref[1])
+
+
+def test_sampler_degenerate_inputs():
     from mickey_amd import ops
     dev = _dev()
     p = torch.zeros((2, 5000))
