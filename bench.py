@@ -10,13 +10,18 @@ read).  Weak scaling: every rank processes its own B pairs.
 rendezvous on 127.0.0.1) unless the script already runs under torch.distributed.run; it fails loudly when
 the node has fewer than N GPUs.  ``n_gpus`` in the output is the number of ranks RCCL saw.
 
-Rank 0 prints ONE COMPACT JSON line (< 3 KB: the driver keeps an 8-KB tail of stdout) as the LAST line of stdout with
+Rank 0 prints ONE COMPACT JSON line (< 3 KB: the driver keeps an 8-KB tail of stdout) as the LAST line of stdout.  A plain
+run does only what the headline needs: it sets up, runs the W warm-up and K timed steps, writes --dump-outputs and prints
+the line with the headline (`value`, `ms_per_step`: the K timed steps) and
   roofline     -- the dominant kernel (the 16-bit MFMA GEMM of the encoder linears): algorithmic FLOPs of
                   the launches in the timed region / their summed HIP-event durations, vs 2.5 PFLOP/s; `traffic` = HBM-side
                   bytes per launch from the committed PMC passes of the same kernel sources (profiles/pmc_traffic.json: a
-                  per-source-hash constant); `peak_sustained` / `frac_sustained` = what the MFMA instruction alone
-                  sustained on this box straight after the timed region (mk_dev_mfma_sustained; information, never `peak`)
+                  per-source-hash constant).  A forward replayed as a hipGraph (batches of <= 4 pairs) bypasses the events:
+                  its roofline needs one extra eager step, taken under --full only
   stages       -- the six largest stages: ms per step and fraction of their governing peak
+``--full`` adds every measurement that takes runs of its own (about a minute at B = 32):
+  peak_sustained / frac_sustained (in roofline) -- what the MFMA instruction alone sustained on this box straight after the
+                  timed region (mk_dev_mfma_sustained; information, never `peak`)
   cpu_baseline -- the CPU oracle (torch-CPU fp32 restatement of the reference) timed on this box's host
                   cores on a bounded sample (1 pair; 1 warm-up, then the median of 3 runs; per-stage seconds), N = 1 only
   sustained_60 -- the headline configuration over 60 back-to-back steps straight after the timed region, pairs/s
@@ -25,9 +30,9 @@ Rank 0 prints ONE COMPACT JSON line (< 3 KB: the driver keeps an 8-KB tail of st
   natural_operands -- the same forward on 1/f-spectrum images and massive-activation weights (leg `natural`): pairs/s and the
                   encoder GEMM's TFLOP/s; information about the power limit, never `value`
   single_pair_ms -- BASELINE.json configs[1]: one 540x720 pair, hipGraph replay
-Everything else -- the full per-stage roofline list, every leg (--legs all: fp16 everywhere, ref_split, ref_split_fp32mfma,
-attn_mfma16, vit_small, config5, natural), --include-h2d (PCIe-inclusive), --precision (errors vs the oracle
-outputs of the same run) -- goes to gpurun_out/bench_detail.json (--detail PATH) and is summarised on stderr.
+Everything else -- the full per-stage roofline list, and under --full every leg (--legs all: fp16 everywhere, ref_split,
+ref_split_fp32mfma, attn_mfma16, vit_small, config5, natural), --include-h2d (PCIe-inclusive), --precision (errors vs the
+oracle outputs of the same run) -- goes to the detail file (--detail PATH) and is summarised on stderr.
 
 ``--dump-outputs DIR`` writes the outputs of the last timed step as DIR/<name>.npy (dump_outputs: at most 64 MB, a seeded
 sample of the larger ones); the inputs are seeded, so two builds run with the same arguments can be compared file by file.
@@ -377,23 +382,26 @@ def parse_args(argv=None):
                     help="AMD.HEADS_DTYPE of the headline model: operand type of the four head stacks (auto = fp16 beside a "
                          "16-bit encoder; the reference runs them in fp32)")
     ap.add_argument("--no-pin", action="store_true", help="N > 1: do not pin the ranks to their GPUs' NUMA cores")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, every measurement that takes runs of its own: the MFMA-alone probe, 60 sustained "
+                         "steps, one pair, the --legs, the CPU baseline (N = 1); without it only the headline is measured")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-threads-probe", action="store_true", help="CPU leg: also time a small pair at os.cpu_count() threads "
                                                                      "(minutes on a 256-core host)")
     ap.add_argument("--no-kernel-events", action="store_true")
-    ap.add_argument("--legs", default="ref_split,natural",
-                    help="comma-separated extra legs, each a full timed run written to the detail file: fp16, ref_split, "
+    ap.add_argument("--legs", default=None,
+                    help="--full: comma-separated extra legs, each a full timed run written to the detail file: fp16, ref_split, "
                          "ref_split_fp32mfma, attn_mfma16, vit_small, config5, natural; 'all'; 'none'.  Default: ref_split (the "
                          "reference's literal precision split, reported in the line as value_ref_precision) and natural (1/f "
                          "images + massive-activation weights: natural_operands of the line)")
     ap.add_argument("--sustained", action="store_true", help="(default since round 6; kept for old command lines)")
     ap.add_argument("--no-sustained", action="store_true", help="skip the 60-step run of the headline configuration ('sustained_60' of the line)")
     ap.add_argument("--precision", action="store_true",
-                    help="also report every feature output's error vs the CPU oracle outputs of this run (detail file)")
-    ap.add_argument("--lean", action="store_true", help="only the headline measurement: no legs, no single-pair / CPU legs "
-                                                         "(profiling passes)")
+                    help="--full: also report every feature output's error vs the CPU oracle outputs of this run (detail file)")
+    ap.add_argument("--lean", action="store_true", help="only the headline measurement (what a run without --full does; kept for "
+                                                         "old command lines)")
     ap.add_argument("--include-h2d", action="store_true",
-                    help="also report the PCIe-inclusive rate under 'pcie_inclusive' (detail file): uint8 frames from host "
+                    help="--full: also report the PCIe-inclusive rate under 'pcie_inclusive' (detail file): uint8 frames from host "
                          "memory through the input pipeline (pinned ring, H2D, resize kernel) into the forward; never `value`")
     ap.add_argument("--no-single", action="store_true", help="skip the one-pair latency leg reported as 'single_pair_ms'")
     ap.add_argument("--detail", default=None, help="path of the detail JSON (default gpurun_out/bench_detail.json; 'none' = do not write)")
@@ -416,11 +424,19 @@ def parse_args(argv=None):
     args = ap.parse_args(argv)
     if args.steps < 1:
         ap.error("--steps must be >= 1")
+    if args.lean and args.full:
+        ap.error("--lean and --full exclude each other")
     args.sustained = not args.no_sustained
-    if args.lean:
+    if not args.full:
+        extra = [opt for opt, on in (("--legs", args.legs not in (None, "none", "")), ("--precision", args.precision),
+                                     ("--include-h2d", args.include_h2d), ("--cpu-threads-probe", args.cpu_threads_probe)) if on]
+        if extra:
+            ap.error("%s only with --full" % ", ".join(extra))
         args.no_single = args.no_cpu_baseline = True
-        args.include_h2d = args.sustained = args.precision = False
+        args.sustained = False
         args.legs = "none"
+    elif args.legs is None:
+        args.legs = "ref_split,natural"
     all_legs = ("fp16", "ref_split", "ref_split_fp32mfma", "attn_mfma16", "vit_small", "config5", "natural")
     args.leg_set = set(all_legs) if args.legs == "all" else set() if args.legs in ("none", "") else set(args.legs.split(","))
     unknown = args.leg_set - set(all_legs)
@@ -746,7 +762,7 @@ def main(argv=None):
         dump_last_step(args.dump_outputs, last, poses, data0)
     graphed = len(model._graphs) > 0
     ev_steps = args.steps
-    if graphed and prof is not None:
+    if graphed and prof is not None and args.full:
         # a replayed graph bypasses the Python-level launch wrappers: time the launches of ONE extra eager step
         mode_was, model.graph_mode = model.graph_mode, False
         prof.on = True
@@ -768,7 +784,7 @@ def main(argv=None):
         if prof is not None and prof.records:
             stages, by = prof.summary(ev_steps)
             roof = roofline_entry(stages, by, B, args.dtype, model)
-            if roof is not None and not args.lean:   # (--lean is what the rocprofv3 passes run: no probe kernel in their statistics)
+            if roof is not None and args.full:   # (a plain run is what the rocprofv3 passes run: no probe kernel in their statistics)
                 # what the socket power limit lets through the matrix pipe ALONE on this box right now (register-resident
                 # pseudo-random bf16 operands, no memory traffic; mickey_hip_dev.h, LABNOTES R4.11): the ceiling of the MFMA
                 # instruction itself next to the 2.5 PFLOP/s spec that `frac` is quoted against.  Never `peak`.
@@ -819,7 +835,7 @@ def main(argv=None):
                                   "hip_graph": len(model._graphs) > 0, "what": "BASELINE.json configs[1]: batch of one pair, same model"}
         except Exception as e:   # extra information: must not cost the headline line
             out["single_pair"] = {"error": "%s: %s" % (type(e).__name__, str(e)[:300])}
-    if single:
+    if single and args.full:
         tick("single pair measured")
     if single and args.include_h2d:
         from mickey_amd import input_pipeline as ip
@@ -899,7 +915,8 @@ def main(argv=None):
         args.dtype, args.steps, args.warmup, outliers=True, natural=True)
 
     if rank == 0:
-        tick("legs measured")
+        if args.full:
+            tick("legs measured")
         if world == 1 and not args.no_cpu_baseline:
             try:
                 cpu_baseline.threads_probe = bool(args.cpu_threads_probe)

@@ -131,16 +131,26 @@ def test_stub_line_is_last_and_small():
 
 
 def test_default_arguments_keep_the_driver_run_short():
-    """The default run = headline + 60 sustained steps + ref_split and natural-operands legs + one-pair leg + CPU baseline (59 s on
-    the box, profiles/r06i_*); everything else is opt-in."""
-    a = bench.parse_args([])
+    """A plain run = the headline alone (warm-up, timed steps, the line); --full = headline + 60 sustained steps + ref_split and
+    natural-operands legs + one-pair leg + CPU baseline (59 s on the box, profiles/r06i_*); everything else is opt-in under --full."""
+    plain = bench.parse_args([])
+    assert not plain.full and plain.leg_set == set() and plain.no_cpu_baseline and plain.no_single and not plain.sustained
+    assert not plain.include_h2d and not plain.precision
+    a = bench.parse_args(["--full"])
     assert a.leg_set == {"ref_split", "natural"} and a.sustained and not a.include_h2d and not a.precision
-    assert not bench.parse_args(["--no-sustained"]).sustained
-    assert bench.parse_args(["--legs", "all"]).leg_set >= {"fp16", "ref_split", "vit_small", "config5"}
+    assert not a.no_cpu_baseline and not a.no_single
+    assert not bench.parse_args(["--full", "--no-sustained"]).sustained
+    assert bench.parse_args(["--full", "--legs", "all"]).leg_set >= {"fp16", "ref_split", "vit_small", "config5"}
     lean = bench.parse_args(["--lean"])
     assert lean.leg_set == set() and lean.no_cpu_baseline and lean.no_single and not lean.sustained
+    assert dict(vars(lean), lean=False) == vars(plain)
     with pytest.raises(SystemExit):
         bench.parse_args(["--legs", "nonsense"])
+    with pytest.raises(SystemExit):
+        bench.parse_args(["--full", "--legs", "nonsense"])
+    for extra in (["--legs", "all"], ["--precision"], ["--include-h2d"], ["--cpu-threads-probe"], ["--lean", "--full"]):
+        with pytest.raises(SystemExit):   # what only --full measures is refused, not dropped, on a plain run
+            bench.parse_args(extra)
 
 
 def test_compact_line_at_eight_gpus_stays_small():

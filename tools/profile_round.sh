@@ -1,32 +1,34 @@
 #!/bin/bash
 # Round evidence for the build that is benchmarked (run on the GPU box through gpurun):
-#   1. (last, once the traffic file exists) the default bench line -> gpurun_out/${TAG}_bench_b32.json
-#   2. rocprofv3 --kernel-trace --stats of bench.py --steps 5   -> gpurun_out/${TAG}_bench_b32_kernel_stats.csv (+ the line under rocprof)
+#   1. (last, once the traffic file exists) the --full bench line -> $OUT/${TAG}_bench_b32.json
+#   2. rocprofv3 --kernel-trace --stats of bench.py --steps 5   -> $OUT/${TAG}_bench_b32_kernel_stats.csv (+ the line under rocprof)
 #   3. PMC passes of the same workload, one counter group per pass (TCC: FETCH_SIZE costs 3 of 4 slots, WRITE_SIZE 2;
-#      never combined with other trace domains), post-processed per kernel ROLE -> gpurun_out/${TAG}_pmc_traffic.json
-#      (FETCH_SIZE / WRITE_SIZE, read by bench.py when its source hash matches) and gpurun_out/${TAG}_pmc_busy.json
+#      never combined with other trace domains), post-processed per kernel ROLE -> $OUT/${TAG}_pmc_traffic.json
+#      (FETCH_SIZE / WRITE_SIZE, read by bench.py when its source hash matches) and $OUT/${TAG}_pmc_busy.json
 #      (SQ_VALU_MFMA_BUSY_CYCLES against GRBM_GUI_ACTIVE)
-# Copy what should be judged from gpurun_out/ to profiles/.
+# OUT: the folder the outputs go to.  Copy what should be judged from $OUT/ to profiles/.
 TAG=${TAG:-r05}
 STEPS_BENCH=${STEPS_BENCH:-20}
 export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
-mkdir -p $R/gpurun_out
+OUT=${OUT:?OUT: the folder this call writes its outputs to}
+mkdir -p "$OUT" && OUT=$(cd "$OUT" && pwd)   # absolute: the passes below run from /tmp
 cd $R
 cd /tmp
 rm -rf /tmp/prof_$TAG
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_$TAG -o p -- python $R/bench.py --steps 5 --warmup 2 --lean > /tmp/prof_$TAG.log 2>&1
-grep "^{\"metric\"" /tmp/prof_$TAG.log | tail -1 > $R/gpurun_out/${TAG}_bench_b32_under_rocprof.json
-cp $(ls /tmp/prof_$TAG/*kernel_stats.csv | head -1) $R/gpurun_out/${TAG}_bench_b32_kernel_stats.csv
+grep "^{\"metric\"" /tmp/prof_$TAG.log | tail -1 > $OUT/${TAG}_bench_b32_under_rocprof.json
+cp $(ls /tmp/prof_$TAG/*kernel_stats.csv | head -1) $OUT/${TAG}_bench_b32_kernel_stats.csv
 for c in FETCH_SIZE WRITE_SIZE "SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_BUSY_CYCLES"; do
   tag=$(echo $c | cut -d' ' -f1)
   rm -rf /tmp/pmc_$tag
   timeout 900 rocprofv3 --kernel-trace --pmc $c --output-format csv -d /tmp/pmc_$tag -o p -- python $R/bench.py --steps 1 --warmup 1 --lean --no-kernel-events > /tmp/pmc_$tag.log 2>&1 || tail -3 /tmp/pmc_$tag.log
 done
-TAG=$TAG python - <<'PY'
+TAG=$TAG OUT=$OUT python - <<'PY'
 import collections, csv, glob, json, os, re, sys
 R = os.environ["GRAFT_REPO_ROOT"]
 TAG = os.environ["TAG"]
+OUT = os.environ["OUT"]
 sys.path.insert(0, R)
 from mickey_amd import build as B
 
@@ -86,7 +88,7 @@ if enc:
     traffic["encoder_gemm"] = {"launches": n,
                                "FETCH_SIZE_KiB_per_launch": sum(roles[k]["FETCH_SIZE_KiB_per_launch"] * roles[k]["launches"] for k in enc) / n,
                                "WRITE_SIZE_KiB_per_launch": sum(roles[k]["WRITE_SIZE_KiB_per_launch"] * roles[k]["launches"] for k in enc) / n}
-json.dump(traffic, open("%s/gpurun_out/%s_pmc_traffic.json" % (R, TAG), "w"), indent=1)
+json.dump(traffic, open("%s/%s_pmc_traffic.json" % (OUT, TAG), "w"), indent=1)
 busy = dict(meta)
 b = collect("SQ_VALU_MFMA_BUSY_CYCLES", ("SQ_VALU_MFMA_BUSY_CYCLES", "GRBM_GUI_ACTIVE", "SQ_BUSY_CYCLES"))
 busy["roles"] = {}
@@ -98,14 +100,14 @@ for k, d in sorted(b.items()):
     # SQ_VALU_MFMA_BUSY_CYCLES is summed over the 1024 SIMDs, GRBM_GUI_ACTIVE over the 8 XCDs (profiles/r01_pmc_busy.md)
     busy["roles"][k] = {"launches": len(m), "SQ_VALU_MFMA_BUSY_CYCLES": mm, "GRBM_GUI_ACTIVE": gg,
                         "mfma_busy_frac": (mm / 1024.0) / (gg / 8.0)}
-json.dump(busy, open("%s/gpurun_out/%s_pmc_busy.json" % (R, TAG), "w"), indent=1)
+json.dump(busy, open("%s/%s_pmc_busy.json" % (OUT, TAG), "w"), indent=1)
 print(json.dumps({"traffic_roles": {k: v for k, v in roles.items() if "gemm" in k or "attention" in k}, "busy": busy["roles"]}, indent=1)[:3000])
 PY
 # the bench line LAST, with the traffic file of this very build in place (bench.py reads profiles/pmc_traffic.json when the
 # source hash matches), so that the line carries roofline.traffic and the per-stage traffic
 cd $R
-cp gpurun_out/${TAG}_pmc_traffic.json profiles/pmc_traffic.json   # (the file name bench.py reads: TRAFFIC_SOURCE)
+cp $OUT/${TAG}_pmc_traffic.json profiles/pmc_traffic.json   # (the file name bench.py reads: TRAFFIC_SOURCE)
 if [ -z "$SKIP_BENCH" ]; then
-  timeout 900 python bench.py --steps $STEPS_BENCH --warmup 5 --detail gpurun_out/${TAG}_bench_detail.json 2>gpurun_out/${TAG}_bench.err | tail -1 > gpurun_out/${TAG}_bench_b32.json
+  timeout 900 python bench.py --full --steps $STEPS_BENCH --warmup 5 --detail $OUT/${TAG}_bench_detail.json 2>$OUT/${TAG}_bench.err | tail -1 > $OUT/${TAG}_bench_b32.json
 fi
-head -c 900 $R/gpurun_out/${TAG}_bench_b32.json; echo; head -6 $R/gpurun_out/${TAG}_bench_b32_kernel_stats.csv | cut -c1-200
+head -c 900 $OUT/${TAG}_bench_b32.json; echo; head -6 $OUT/${TAG}_bench_b32_kernel_stats.csv | cut -c1-200
