@@ -147,6 +147,18 @@ int mk_layernorm(const float* x, int ldx, const float* w, const float* b, float 
                  float* resid, int ldr, int rows_out, int D, int rows_per_img, int skip, int wgroup_rows, int bord_h,
                  int bord_w, int bord_m, int dtype, mk_stream_t stream);
 
+/* The encoder's final LayerNorm written CHANNEL-major with the CLS row dropped: what a torch Conv2d stack reads (the
+ * reference's heads in a training step: dinov2.py:230-233 x_norm_patchtokens, then mickey_extractor.py:49-52
+ * .permute(0, 2, 1).reshape(B, C, h, w).float()).  x fp32 [*, ldx], out fp32 [nimg, D, npix]:
+ *   out[(img * D + c) * npix + p] = LN_D(x[(img * rows_per_img + skip + p) * ldx + 0..D-1])[c] * w[c] + b[c]
+ * Every value is bit-identical to mk_layernorm's fp32 output of the same rows (same statistics in the same summation order,
+ * same normalisation expression; the D <= 128 and D > 128 forms as mk_layernorm dispatches them).  round_fp16 != 0: each value
+ * is additionally rounded to the nearest fp16 (ties to even, overflow to inf, NaN kept) and widened back -- what the
+ * reference's fp16 encoder hands its heads through .float().  D % 4 == 0, D <= 2048, ldx % 4 == 0, rows_per_img >= skip + npix;
+ * x, w and b 16-byte aligned (read as float4, as in mk_layernorm; not checked), out 4-byte aligned; npix is arbitrary.  Deterministic, one writer per element, nothing outside out[0 .. nimg * D * npix) is written. */
+int mk_layernorm_nchw(const float* x, int ldx, const float* w, const float* b, float eps, float* out, int nimg, int npix, int D,
+                      int rows_per_img, int skip, int round_fp16, mk_stream_t stream);
+
 /* A 128-wide linear and the LayerNorm behind it in one pass (the linear-attention layers of the heads: merge -> norm1 and
  * mlp[2] -> norm2 + the layer's residual, att_layers/transformer_utils.py:58-66): per group g and row r
  *   y = LayerNorm_128(A[g][r, :K] . W[g]^T) * ln_w[g] + ln_b[g];   resid != NULL: resid[g*M + r] += y, out = the updated resid

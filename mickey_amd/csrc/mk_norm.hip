@@ -29,6 +29,51 @@ constexpr int LN_MAXV = 8;  // float4 per lane -> D <= 2048 (instantiated for 4 
 constexpr int LN_RPW = 4;   // rows per wave: the loads of row r+1 are in flight while row r is reduced and stored
                             // (a third buffer / 6 rows per wave measured 7 % slower in the forward)
 
+// ---- the per-row arithmetic: ONE statement of it for every kernel that has to write the same bits (mk_layernorm and
+// mk_layernorm_nchw are compared with torch.equal): same summation order, same contraction of the normalisation ----
+// wide form: a row is a wave, lane l holds columns (i * 64 + l) * 4 ..
+template <int MAXV>
+__device__ __forceinline__ void ln_row_stats(const f32x4 (&cur)[MAXV], int lane, int D, float eps, float& mean, float& rstd) {
+  float s = 0.f;
+#pragma unroll
+  for (int i = 0; i < MAXV; ++i) {
+    const int c = (i * 64 + lane) * 4;
+    if (c < D) s += (cur[i][0] + cur[i][1]) + (cur[i][2] + cur[i][3]);
+  }
+  mean = wave_sum(s) / (float)D;
+  float q = 0.f;
+#pragma unroll
+  for (int i = 0; i < MAXV; ++i) {
+    const int c = (i * 64 + lane) * 4;
+    if (c < D) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const float d = cur[i][e] - mean;
+        q += d * d;
+      }
+    }
+  }
+  rstd = 1.0f / sqrtf(wave_sum(q) / (float)D + eps);
+}
+
+// narrow form (D <= 128): a row is 32 lanes x 4 floats, the sums run over a half wave; v is zero in lanes without a column
+__device__ __forceinline__ float ln_half_sum(float a) {
+#pragma unroll
+  for (int o = 16; o > 0; o >>= 1) a += __shfl_xor(a, o, 64);
+  return a;
+}
+// d: the centred values v - mean (zero in lanes without a column), which the caller normalises with ln_scale
+__device__ __forceinline__ void ln_narrow_stats(const f32x4& v, bool cok, int D, float eps, float& mean, float& rstd, f32x4& d) {
+  mean = ln_half_sum((v[0] + v[1]) + (v[2] + v[3])) / (float)D;
+  d = f32x4{0.f, 0.f, 0.f, 0.f};
+  if (cok) d = v - mean;
+  rstd = 1.0f / sqrtf(ln_half_sum(d[0] * d[0] + d[1] * d[1] + d[2] * d[2] + d[3] * d[3]) / (float)D + eps);
+}
+
+// one element of the normalised row, both forms: from the centred value, or from x (the same subtraction, then the same rest)
+__device__ __forceinline__ float ln_scale(float d, float rstd, float w, float b) { return d * rstd * w + b; }
+__device__ __forceinline__ float ln_norm(float x, float mean, float rstd, float w, float b) { return ln_scale(x - mean, rstd, w, b); }
+
 template <typename T, int MAXV>
 __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict__ x, int ldx, const float* __restrict__ w,
                                                         const float* __restrict__ b, float eps, void* out, int ldo,
@@ -82,26 +127,8 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
       wr += (long long)(r / wgroup_rows) * D;
       br += (long long)(r / wgroup_rows) * D;
     }
-    float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < MAXV; ++i) {
-      const int c = (i * 64 + lane) * 4;
-      if (c < D) s += (cur[i][0] + cur[i][1]) + (cur[i][2] + cur[i][3]);
-    }
-    const float mean = wave_sum(s) / (float)D;
-    float q = 0.f;
-#pragma unroll
-    for (int i = 0; i < MAXV; ++i) {
-      const int c = (i * 64 + lane) * 4;
-      if (c < D) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const float d = cur[i][e] - mean;
-          q += d * d;
-        }
-      }
-    }
-    const float rstd = 1.0f / sqrtf(wave_sum(q) / (float)D + eps);
+    float mean, rstd;
+    ln_row_stats<MAXV>(cur, lane, D, eps, mean, rstd);
 #pragma unroll
     for (int i = 0; i < MAXV; ++i) {
       const int c = (i * 64 + lane) * 4;
@@ -109,7 +136,7 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
         const f32x4 ww = shared_wb ? wreg[i] : *(const f32x4*)(wr + c), bb = shared_wb ? breg[i] : *(const f32x4*)(br + c);
         f32x4 y;
 #pragma unroll
-        for (int e = 0; e < 4; ++e) y[e] = (cur[i][e] - mean) * rstd * ww[e] + bb[e];
+        for (int e = 0; e < 4; ++e) y[e] = ln_norm(cur[i][e], mean, rstd, ww[e], bb[e]);
         if (resid) {
           float* rp = resid + (long long)r * ldr + c;
           y += *(const f32x4*)rp;
@@ -158,25 +185,19 @@ __global__ __launch_bounds__(256) void layernorm_narrow_kernel(const float* __re
       v[t] = __builtin_nontemporal_load((const f32x4*)(x + rin * ldx + c));
     }
   }
-  auto half_sum = [](float a) {
-#pragma unroll
-    for (int o = 16; o > 0; o >>= 1) a += __shfl_xor(a, o, 64);
-    return a;
-  };
 #pragma unroll
   for (int t = 0; t < LNN_TRIPS; ++t) {
     const int r = r0 + 2 * t + half;
     const bool ok = r < rows_out && cok;
-    const float mean = half_sum((v[t][0] + v[t][1]) + (v[t][2] + v[t][3])) / (float)D;
-    f32x4 d = f32x4{0.f, 0.f, 0.f, 0.f};
-    if (cok) d = v[t] - mean;
-    const float rstd = 1.0f / sqrtf(half_sum(d[0] * d[0] + d[1] * d[1] + d[2] * d[2] + d[3] * d[3]) / (float)D + eps);
+    float mean, rstd;
+    f32x4 d;
+    ln_narrow_stats(v[t], cok, D, eps, mean, rstd, d);
     if (!ok) continue;
     const long long wo = wgroup_rows > 0 ? (long long)(r / wgroup_rows) * D : 0;
     const f32x4 ww = *(const f32x4*)(w + wo + c), bb = *(const f32x4*)(b + wo + c);
     f32x4 y;
 #pragma unroll
-    for (int e = 0; e < 4; ++e) y[e] = d[e] * rstd * ww[e] + bb[e];
+    for (int e = 0; e < 4; ++e) y[e] = ln_scale(d[e], rstd, ww[e], bb[e]);
     if (resid) {
       float* rp = resid + (long long)r * ldr + c;
       y += *(const f32x4*)rp;
@@ -199,6 +220,129 @@ __global__ __launch_bounds__(256) void layernorm_narrow_kernel(const float* __re
         *(typename Lp<T>::V4*)((T*)out + ro * ldo + c) = o;
       }
     }
+  }
+}
+
+// The final norm written CHANNEL-major (mickey_hip.h, mk_layernorm_nchw): out[img][c][p], fp32.  A workgroup owns 64 pixels
+// of one image -- the 256-byte store runs -- and every channel of them.
+//   pass 1  the row statistics, exactly as the kernels above form them (ln_row_stats / ln_narrow_stats: a row per wave, or per
+//           half wave for D <= 128); (mean, rstd) of the 64 rows stay in LDS.  Plain loads: the rows are wanted again.
+//   pass 2  128 channels at a time: the rows are read a second time (by the workgroup that just read them: out of the cache
+//           hierarchy, not HBM; streamed this time), normalised with ln_norm, written TRANSPOSED into a [128][64 + 1] LDS tile,
+//           and the tile leaves as one 64-pixel run per channel, a wave per run.
+// LDS banks (32 for every ds_write and for ds_read_b32, lanes conflict within a 32-lane half): a half wave of the transposing
+// write holds 16 channel quads x 2 pixels, dword address (4 cq + e) * 65 + p = 4 cq + e + p (mod 32): cq and cq + 8 share a
+// bank, nothing else does -- 2-way, which a ds_write_b32 hides behind its own data transfer; the read-out's half wave reads 32
+// consecutive dwords of one tile row.  33.8 KB per workgroup: four workgroups per CU.
+constexpr int NCHW_TP = 64;            // pixels per workgroup
+constexpr int NCHW_CC = 128;           // channels per LDS round
+constexpr int NCHW_LD = NCHW_TP + 1;   // tile row pitch in dwords (odd: see above)
+template <int MAXV, bool NARROW>
+__global__ __launch_bounds__(256) void layernorm_nchw_kernel(const float* __restrict__ x, int ldx, const float* __restrict__ w,
+                                                             const float* __restrict__ b, float eps, float* __restrict__ out,
+                                                             int npix, int D, int rows_per_img, int skip, int tiles, int round_fp16) {
+  __shared__ float tile[NCHW_CC * NCHW_LD];
+  __shared__ float s_mean[NCHW_TP], s_rstd[NCHW_TP];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int img = blockIdx.x / tiles, p0 = (blockIdx.x - img * tiles) * NCHW_TP;
+  const int np = min(NCHW_TP, npix - p0);   // pixels of this tile
+  const float* xt = x + ((long long)img * rows_per_img + skip + p0) * ldx;
+  if constexpr (NARROW) {
+    constexpr int TRIPS = NCHW_TP / 8;   // row pairs per wave, LNN_TRIPS of them in flight at a time
+    const int half = lane >> 5, c = (lane & 31) * 4;
+    const bool cok = c < D;
+#pragma unroll 1
+    for (int t0 = 0; t0 < TRIPS; t0 += LNN_TRIPS) {
+      f32x4 v[LNN_TRIPS];
+#pragma unroll
+      for (int t = 0; t < LNN_TRIPS; ++t) {
+        const int p = (wave * TRIPS + t0 + t) * 2 + half;
+        v[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+        if (p < np && cok) v[t] = *(const f32x4*)(xt + (long long)p * ldx + c);
+      }
+#pragma unroll
+      for (int t = 0; t < LNN_TRIPS; ++t) {
+        const int p = (wave * TRIPS + t0 + t) * 2 + half;
+        float mean, rstd;
+        f32x4 d;
+        ln_narrow_stats(v[t], cok, D, eps, mean, rstd, d);
+        if ((lane & 31) == 0 && p < np) {
+          s_mean[p] = mean;
+          s_rstd[p] = rstd;
+        }
+      }
+    }
+  } else {
+    constexpr int RPW = NCHW_TP / 4;   // rows per wave: p = rr * 4 + wave, the next row in flight while this one is reduced
+    f32x4 v[2][MAXV];
+    auto load_row = [&](int p, f32x4 (&dst)[MAXV]) {
+      const float* xr = xt + (long long)p * ldx;
+#pragma unroll
+      for (int i = 0; i < MAXV; ++i) {
+        const int c = (i * 64 + lane) * 4;
+        if (c < D) dst[i] = *(const f32x4*)(xr + c);
+      }
+    };
+    auto step = [&](int p, f32x4 (&cur)[MAXV], f32x4 (&nxt)[MAXV]) {   // p is wave-uniform: the shuffles see whole waves
+      if (p >= np) return;
+      if (p + 4 < np) load_row(p + 4, nxt);
+      float mean, rstd;
+      ln_row_stats<MAXV>(cur, lane, D, eps, mean, rstd);
+      if (lane == 0) {
+        s_mean[p] = mean;
+        s_rstd[p] = rstd;
+      }
+    };
+    if (wave < np) load_row(wave, v[0]);
+#pragma unroll 1
+    for (int rr = 0; rr < RPW; rr += 2) {   // (rolled: unrolled, the compiler hoists all 16 rows' loads and the kernel needs 300 registers)
+      step(rr * 4 + wave, v[0], v[1]);
+      step(rr * 4 + 4 + wave, v[1], v[0]);
+    }
+  }
+  __syncthreads();
+#pragma unroll 1
+  for (int c0 = 0; c0 < D; c0 += NCHW_CC) {
+#pragma unroll 1
+    for (int hb = 0; hb < NCHW_CC / 64; ++hb) {   // 64 channels x 64 pixels per trip: 16 quads x 16 pixels per step
+      const int cl = hb * 64 + (tid & 15) * 4, c = c0 + cl;
+      if (c < D) {
+        const f32x4 ww = *(const f32x4*)(w + c), bb = *(const f32x4*)(b + c);
+        f32x4 xv[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const int p = j * 16 + (tid >> 4);
+          if (p < np) xv[j] = __builtin_nontemporal_load((const f32x4*)(xt + (long long)p * ldx + c));
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const int p = j * 16 + (tid >> 4);
+          if (p < np) {
+            const float mean = s_mean[p], rstd = s_rstd[p];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+              float y = ln_norm(xv[j][e], mean, rstd, ww[e], bb[e]);
+              if (round_fp16) {
+                // the fp32 value is rounded FIRST (as mk_layernorm writes it), then to fp16: left to itself hipcc fuses ln_norm's
+                // fma and the conversion into one v_fma_mixlo_f16 -- a single rounding, which is not tensor.half() of the fp32 value
+                asm volatile("" : "+v"(y));
+                y = (float)(_Float16)y;   // nearest even, overflow to inf, NaN stays NaN
+              }
+              tile[(cl + e) * NCHW_LD + p] = y;
+            }
+          }
+        }
+      }
+    }
+    __syncthreads();
+#pragma unroll 8
+    for (int it = 0; it < NCHW_CC * NCHW_TP / 256; ++it) {
+      const int idx = it * 256 + tid;
+      const int cl = idx >> 6, p = idx & (NCHW_TP - 1);   // a wave = one channel's run of 64 pixels
+      const int c = c0 + cl;
+      if (p < np && c < D) out[((long long)img * D + c) * npix + p0 + p] = tile[cl * NCHW_LD + p];
+    }
+    __syncthreads();
   }
 }
 
@@ -373,6 +517,28 @@ int mk_layernorm_planes(const float* x, int ldx, const float* w, const float* b,
   MK_CHECK_ARG(out_hi, "mk_layernorm_planes: null plane pointer");
   return layernorm_launch(x, ldx, w, b, eps, out_hi, ldo, 2, resid, ldr, rows_out, D, rows_per_img, skip, wgroup_rows, bord_h, bord_w,
                           bord_m, MK_F32, out_lo, plane_scale, sat_flag, stream);
+}
+
+int mk_layernorm_nchw(const float* x, int ldx, const float* w, const float* b, float eps, float* out, int nimg, int npix, int D,
+                      int rows_per_img, int skip, int round_fp16, mk_stream_t stream) {
+  MK_CHECK_ARG(x && w && b && out, "mk_layernorm_nchw: null pointer");
+  MK_CHECK_ARG(D > 0 && D % 4 == 0 && D <= LN_MAXV * 256, "mk_layernorm_nchw: D=%d must be a multiple of 4 and <= %d", D,
+               LN_MAXV * 256);
+  MK_CHECK_ARG(nimg > 0 && npix > 0 && skip >= 0 && rows_per_img >= skip + npix && ldx >= D && ldx % 4 == 0,
+               "mk_layernorm_nchw: bad geometry (nimg=%d npix=%d rows_per_img=%d skip=%d ldx=%d)", nimg, npix, rows_per_img, skip, ldx);
+  const int tiles = (npix + NCHW_TP - 1) / NCHW_TP;
+  MK_CHECK_ARG((long long)nimg * tiles <= 0x7fffffffLL, "mk_layernorm_nchw: too many tiles");
+  const dim3 grid((unsigned)(nimg * tiles));
+#define MK_LNT(V_, N_)                                                                                                      \
+  hipLaunchKernelGGL((layernorm_nchw_kernel<V_, N_>), grid, dim3(256), 0, (hipStream_t)stream, x, ldx, w, b, eps, out, npix, D, \
+                     rows_per_img, skip, tiles, round_fp16 ? 1 : 0)
+  // the arithmetic form follows mk_layernorm's dispatch (layernorm_launch): the two entry points write the same bits
+  if (D <= 128) MK_LNT(4, true);
+  else if (D <= 1024) MK_LNT(4, false);
+  else MK_LNT(LN_MAXV, false);
+#undef MK_LNT
+  MK_CHECK_LAUNCH();
+  return MK_OK;
 }
 
 int mk_im2col_patch14(const float* img, long long stride_img, long long stride_ch, int stride_row, int nimg, int gh,

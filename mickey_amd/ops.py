@@ -169,6 +169,21 @@ def layernorm(x, w, b, eps, out=None, out_dtype=torch.bfloat16, resid=None, rows
     return out
 
 
+def layernorm_nchw(x, w, b, eps, nimg, npix, rows_per_img, skip=1, round_fp16=False, out=None):
+    """mk_layernorm_nchw: LayerNorm of rows skip .. skip + npix of each image's rows_per_img rows of fp32 x [*, D], written
+    channel-major: fp32 [nimg, D, npix], bit-identical to layernorm(..., out_dtype=float32) of the same rows.  round_fp16: every
+    value rounded to fp16 and widened back (tensor.half().float()).  out: a contiguous fp32 tensor of nimg * D * npix elements."""
+    D = w.shape[-1]
+    _chk(x, torch.float32)
+    assert x.shape[-1] == D and x.numel() // D >= nimg * rows_per_img, "x holds fewer than nimg * rows_per_img rows"
+    if out is None:
+        out = torch.empty((nimg, D, npix), device=x.device, dtype=torch.float32)
+    assert out.dtype == torch.float32 and out.is_contiguous() and out.numel() == nimg * D * npix
+    call("mk_layernorm_nchw", ptr(x), x.stride(-2), ptr(w), ptr(b), float(eps), ptr(out), nimg, npix, D, rows_per_img, skip,
+         int(bool(round_fp16)), stream())
+    return out
+
+
 def gemm_ln128(a, w, ln_w, ln_b, eps, out, groups, M, K, lda=None, ldo=None, resid=None, bordered=None):
     """mk_gemm_ln128: out = LayerNorm(a[g] @ w[g]^T) * ln_w[g] + ln_b[g] (+ resid, updated in place) for 128 output features;
     a lp [groups, M, >= K], w lp [groups, 128, K], out lp (dense rows or, bordered = (nimg, H, W), bordered feature maps)."""

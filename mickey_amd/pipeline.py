@@ -34,11 +34,9 @@ class Workspace:
         return t
 
 
-def encoder_forward(W, ws, img):
-    """img fp32 [nimg, 3, H, W] on device (already cropped view or not: the /14 crop is implicit in
-    gh, gw), or a sequence of such tensors of one H x W (the two image sets of a pair batch: patched straight into one
-    token matrix, no concatenated copy of the images).  Returns the final-norm patch tokens, lp, as a bordered feature map
-    of nimg gh x gw grids."""
+def _encoder_trunk(W, ws, img):
+    """Everything of the encoder up to its final norm (shared by encoder_forward and encoder_features: the same launches in
+    the same order on the same workspace buffers).  -> (x fp32 [nimg * ntok, D] (a workspace buffer), nimg, gh, gw)."""
     imgs = list(img) if isinstance(img, (list, tuple)) else [img]
     img = imgs[0]
     dev, lp = img.device, W.lp
@@ -95,6 +93,18 @@ def encoder_forward(W, ws, img):
             ops.layernorm(x, blk.n2w, blk.n2b, 1e-6, out=y)
             ops.gemm(y, blk.fc1_w, blk.fc1_b, act=ops.ACT_GELU, out=hid)
             ops.gemm_ls_residual(hid, blk.fc2_w, blk.fc2_b, blk.g2, x)
+    return x, nimg, gh, gw
+
+
+def encoder_forward(W, ws, img):
+    """img fp32 [nimg, 3, H, W] on device (already cropped view or not: the /14 crop is implicit in
+    gh, gw), or a sequence of such tensors of one H x W (the two image sets of a pair batch: patched straight into one
+    token matrix, no concatenated copy of the images).  Returns the final-norm patch tokens, lp, as a bordered feature map
+    of nimg gh x gw grids."""
+    x, nimg, gh, gw = _encoder_trunk(W, ws, img)
+    dev, lp, D = x.device, W.lp, W.D
+    npatch = gh * gw
+    ntok = npatch + 1
     # the heads' operand type, as a BORDERED feature map (mickey_hip.h: what a 3x3 conv reads; border rows stay zero)
     # (bordered buffers are zeroed ONCE and only their pixel rows are ever written: the key carries the geometry, because two
     # geometries can share a row count while their border rows sit elsewhere)
@@ -113,6 +123,20 @@ def encoder_forward(W, ws, img):
     ops.layernorm(x, W.norm_w, W.norm_b, 1e-6, out=(feat[0], None) if hi_only else feat, rows_out=nimg * npatch, rows_per_img=ntok, skip=1,
                   bordered=(nimg, gh, gw), sat=ws.sat_flag)
     return feat, gh, gw
+
+
+def encoder_features(W, ws, img, round_fp16=False):
+    """The encoder for a torch consumer (the reference's trainable Conv2d heads in a training step, mickey_amd.train_encoder):
+    the trunk of encoder_forward, then the final norm written channel-major by mk_layernorm_nchw.  img as encoder_forward takes
+    it.  Returns fp32 [nimg, D, gh, gw] -- the values of dinov2.py:230-233 x_norm_patchtokens after
+    mickey_extractor.py:49-52's permute / reshape / float(); round_fp16: rounded to fp16 on the way (what an fp16 encoder hands
+    over).  The result is a FRESH tensor on every call, never a workspace buffer: a training step holds image 0's features while
+    image 1 is encoded, and autograd holds both until the heads' backward."""
+    x, nimg, gh, gw = _encoder_trunk(W, ws, img)
+    npatch = gh * gw
+    out = torch.empty((nimg, W.D, gh, gw), dtype=torch.float32, device=x.device)
+    ops.layernorm_nchw(x, W.norm_w, W.norm_b, 1e-6, nimg, npatch, rows_per_img=npatch + 1, skip=1, round_fp16=bool(round_fp16), out=out)
+    return out
 
 
 def heads_forward(W, ws, feat, nimg, gh, gw, cfg):
