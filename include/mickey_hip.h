@@ -249,6 +249,60 @@ int mk_gemm_grouped_split(const void* A_hi, const void* A_lo, int lda, long long
                           const float* bias, long long strideBias, void* out, void* out_lo, int ldc, long long strideOut, int groups,
                           int M, int N, int K, int act, float acc_scale, float plane_scale, int* sat_flag, mk_stream_t stream);
 
+/* ---- Training: the heads' trainable 3x3 convolutions (utils/extractor_utils.py:18-31: nn.Conv2d(k=3, stride=1, padding=1,
+ * bias=False), fp32 forward and backward through autograd).  Forward and input gradient are the split convolution above on operand
+ * planes made on the device every step; the weight gradient is its own GEMM.  Plane scales follow each tensor's abs-max and live
+ * in DEVICE memory: nothing here synchronises with the host.  No atomics: every result is bit-identical from run to run. */
+
+/* mk_conv3x3_split (one source, one group, no bias, no activation, fp32 dense rows out) with the accumulator scale read from
+ * DEVICE memory when the kernels run (utils/extractor_utils.py:18-31 in a training step, where the scale follows a tensor's
+ * abs-max and the host never learns it): out[pix, co] = acc_scale[0] * sum_{tap, ci} W[co, tap * C1 + ci] * in[pix + tap, ci].
+ * The split conv's kernels run with scale 1 and one in-place pass multiplies the rows by acc_scale[0] (a power of two: the same
+ * bits as scaling in the epilogue; a NaN scale makes every output NaN).  in_hi / in_lo: bordered fp16 planes within 2 GiB of each
+ * other; W: fp16 [Cout, ldw] interleaved planes, ldw >= 18 C1; C1 % 32 == 0, Cout % 4 == 0; out 16-byte aligned. */
+int mk_conv3x3_split_dscale(const void* in_hi, const void* in_lo, int C1, const void* W, int ldw, float* out, int Cout, int nimg, int H,
+                            int Wd, const float* acc_scale, mk_stream_t stream);
+
+/* Power-of-two plane scale of an fp32 tensor [d0, d1, d2, d3] with element strides s0..s3 (utils/extractor_utils.py:18-31: the
+ * operands of the conv and of its backward): scale[0] = s with max|x| * s in [2^14, 2^15) (exponent clamped to +-100), scale[1] =
+ * 1 / s.  An all-zero tensor gives s = 1; a tensor with an Inf or NaN gives s = 1 and scale[1] = NaN, so that whatever is computed
+ * with its planes comes out non-finite.  Two launches, deterministic.  work: mk_absmax_scale_work_floats() floats; scale: 2. */
+long long mk_absmax_scale_work_floats(void);
+int mk_absmax_scale(const float* x, int d0, int d1, int d2, int d3, long long s0, long long s1, long long s2, long long s3,
+                    float* work, float* scale, mk_stream_t stream);
+
+/* Operand planes of a training conv (utils/extractor_utils.py:18-31).  A plane buffer is a zero-initialised fp16 matrix of
+ * mk_conv_train_plane_rows(nimg, H, Wd) rows whose row mk_conv_train_lead_rows(Wd) is row 0 of the bordered feature map: the
+ * weight-gradient kernel sweeps whole K steps of 32 rows with one row shift per tap and no bounds test, so Wd + 2 rows in front
+ * of the map and the rows behind it up to the buffer's end must exist and be zero.  hi / lo point at bordered row 0.
+ * mk_conv_train_planes: fp32 [nimg, C, H, Wd] with element strides (contiguous, channels_last, sliced ...) -> x * scale[0] = hi +
+ * lo, [.., ld] fp16 (no clamping: an Inf gives Inf / NaN planes); C % 4 == 0, ld % 4 == 0, ld >= C; columns C .. ld - 1 and all
+ * border rows are left alone. */
+long long mk_conv_train_lead_rows(int Wd);
+long long mk_conv_train_plane_rows(int nimg, int H, int Wd);
+int mk_conv_train_planes(const float* src, long long stride_b, long long stride_c, long long stride_h, long long stride_w, int nimg,
+                         int C, int H, int Wd, const float* scale, void* hi, void* lo, int ld, mk_stream_t stream);
+
+/* fp32 weight [Cout, Cin, 3, 3] (contiguous; utils/extractor_utils.py:18-31) -> the interleaved (32 hi | 32 lo) planes of
+ * w * w_scale[0] that mk_conv3x3_split reads (weights.split_conv_weight):
+ *   transposed == 0: fp16 [Cout, 2 * 9 Cin], column tap * Cin + ci -- the forward;
+ *   transposed != 0: fp16 [Cin, 2 * 9 Cp], column tap * Cp + co of w[co, ci, 2 - ky, 2 - kx], Cp = Cout rounded up to 32, zero for
+ *     co >= Cout -- the conv that turns gY's planes [.., Cp] into the input gradient.
+ * acc_scale[0] = w_scale[1] * act_scale[1]: the accumulator scale of that conv (act_scale: the scale of its activation planes).
+ * Cin % 32 == 0, Cout % 4 == 0. */
+int mk_conv_train_weight_planes(const float* w, int Cout, int Cin, int transposed, const float* w_scale, const float* act_scale,
+                                void* planes, float* acc_scale, mk_stream_t stream);
+
+/* Weight gradient of the 3x3 conv (utils/extractor_utils.py:18-31 under autograd):
+ *   dw[co, ci, ky, kx] = sum over bordered rows r of gY[r, co] * X[r + (ky - 1)(Wd + 1) + kx - 1, ci]
+ * gy_hi / gy_lo [.., ldg] and x_hi / x_lo [.., Cin]: plane buffers as above (scales gy_scale, x_scale); ldg % 32 == 0, ldg >= Cout.
+ * Split-fp16 A^T . B on the matrix cores (gY_hi.X_hi + gY_lo.X_hi + gY_hi.X_lo, fp32 accumulation), rows cut into fixed chunks
+ * whose partial sums (work: mk_conv_wgrad_work_floats floats) are added in chunk order.  dw: fp32 [Cout, Cin, 3, 3].
+ * Cin % 32 == 0, Cout % 4 == 0; planes, work and dw 16-byte aligned. */
+long long mk_conv_wgrad_work_floats(int Cout, int Cin, int nimg, int H, int Wd);
+int mk_conv_wgrad(const void* gy_hi, const void* gy_lo, int ldg, const void* x_hi, const void* x_lo, int Cout, int Cin, int nimg, int H,
+                  int Wd, const float* gy_scale, const float* x_scale, float* work, float* dw, mk_stream_t stream);
+
 /* Start of Transformer_self_att (att_layers/transformer.py:92-95): xs = x + pe (fp32 stream) and an
  * lp copy into columns [0,C) of a [rows, ld_cat] buffer.  x lp [G][rows, C]; pe fp32 [npix, C] or NULL. */
 int mk_posenc_add(const void* x, const float* pe, float* xs, void* cat, int ld_cat, int groups, int nimg, int npix, int C,

@@ -42,7 +42,16 @@ SIGNATURES = {
     "mk_bordered_rows": ("l", "iii"),
     "mk_conv3x3": ("i", "pliplipilplplpiliiiiiiip"),
     "mk_conv3x3_split": ("i", "pplipplipilplppiliiiiiiffpp"),
+    "mk_conv3x3_split_dscale": ("i", "ppipipiiiipp"),
     "mk_split_planes": ("i", "plilfpplpp"),
+    "mk_absmax_scale_work_floats": ("l", ""),
+    "mk_absmax_scale": ("i", "piiiillllppp"),
+    "mk_conv_train_lead_rows": ("l", "i"),
+    "mk_conv_train_plane_rows": ("l", "iii"),
+    "mk_conv_train_planes": ("i", "plllliiiipppip"),
+    "mk_conv_train_weight_planes": ("i", "piiippppp"),
+    "mk_conv_wgrad_work_floats": ("l", "iiiii"),
+    "mk_conv_wgrad": ("i", "ppippiiiiippppp"),
     "mk_gemm_grouped_split": ("i", "ppilpilplppiliiiiiffpp"),
     "mk_posenc_add": ("i", "ppppiiiiiip"),
     "mk_linattn_work_floats": ("l", "iiii"),

@@ -314,6 +314,76 @@ def conv3x3_split(in1, C1, w, bias, out, Cout, groups, nimg, H, W, act=ACT_NONE,
     return out
 
 
+# ---- training: the heads' trainable 3x3 convolutions (mickey_hip.h: mk_conv_train_*, mk_conv_wgrad; train_heads.py) -----------
+def absmax_scale(x, work=None):
+    """mk_absmax_scale: fp32 4-d device tensor of any strides -> fp32 [2] device tensor (s, 1 / s), s the power-of-two plane
+    scale that follows the tensor's abs-max.  Stays on the device: no synchronisation."""
+    assert x.dtype == torch.float32 and x.dim() == 4 and x.numel() > 0
+    if work is None:
+        work = torch.empty(int(query("mk_absmax_scale_work_floats")), device=x.device, dtype=torch.float32)
+    scale = torch.empty(2, device=x.device, dtype=torch.float32)
+    if x.is_contiguous() or x.is_contiguous(memory_format=torch.channels_last):   # dense in memory: one flat sweep
+        n = x.numel()
+        dims, strides = (1, 1, 1, n), (n, n, n, 1)
+    else:
+        dims, strides = tuple(x.shape), tuple(x.stride())
+    assert all(d < 2 ** 31 for d in dims), "mk_absmax_scale: a dimension of 2^31 elements or more"
+    call("mk_absmax_scale", ptr(x), *dims, *strides, ptr(work), ptr(scale), stream())
+    return scale
+
+
+def conv_train_plane_buffer(nimg, H, W, C, device):
+    """A zeroed (hi, lo) pair of training plane buffers (one allocation) and the views at bordered row 0 the kernels take:
+    -> (buffer [2, mk_conv_train_plane_rows, C], hi, lo)."""
+    lead, rows = int(query("mk_conv_train_lead_rows", W)), int(query("mk_conv_train_plane_rows", nimg, H, W))
+    buf = torch.zeros((2, rows, C), device=device, dtype=torch.float16)
+    return buf, buf[0, lead:], buf[1, lead:]
+
+
+def conv_train_planes(x, scale, hi, lo):
+    """mk_conv_train_planes: fp32 [nimg, C, H, W] of any strides -> the bordered (hi, lo) planes of x * scale[0]; hi / lo: the views
+    of conv_train_plane_buffer, C <= their width."""
+    nimg, C, H, W = x.shape
+    assert x.dtype == torch.float32 and hi.dtype == torch.float16 and lo.dtype == torch.float16 and hi.stride() == lo.stride()
+    call("mk_conv_train_planes", ptr(x), x.stride(0), x.stride(1), x.stride(2), x.stride(3), nimg, C, H, W, ptr(scale), ptr(hi),
+         ptr(lo), hi.stride(0), stream())
+
+
+def conv_train_weight_planes(w, w_scale, act_scale, transposed=False):
+    """mk_conv_train_weight_planes: contiguous fp32 [Cout, Cin, 3, 3] -> (planes, acc_scale): the interleaved fp16 planes of the
+    forward ([Cout, 2 * 9 Cin]) or, transposed, of the input gradient ([Cin, 2 * 9 Cp], Cp = Cout rounded up to 32), and the fp32
+    [1] accumulator scale 1 / (s_w s_act) of the conv that uses them."""
+    Cout, Cin = w.shape[:2]
+    assert w.dtype == torch.float32 and w.is_contiguous() and tuple(w.shape[2:]) == (3, 3)
+    Cp = (Cout + 31) // 32 * 32
+    planes = torch.empty((Cin, 18 * Cp) if transposed else (Cout, 18 * Cin), device=w.device, dtype=torch.float16)
+    acc = torch.empty(1, device=w.device, dtype=torch.float32)
+    call("mk_conv_train_weight_planes", ptr(w), Cout, Cin, int(bool(transposed)), ptr(w_scale), ptr(act_scale), ptr(planes), ptr(acc),
+         stream())
+    return planes, acc
+
+
+def conv3x3_split_dscale(in1, C1, w, out, Cout, nimg, H, W, acc_scale):
+    """mk_conv3x3_split_dscale, the plain form the training convs use: in1 = (hi, lo) bordered planes, w = interleaved planes,
+    out fp32 dense rows [nimg * H * W, Cout] = acc * acc_scale[0] with acc_scale a device tensor."""
+    h1, l1 = in1
+    assert w.dtype == torch.float16 and out.dtype == torch.float32 and acc_scale.dtype == torch.float32
+    call("mk_conv3x3_split_dscale", ptr(h1), ptr(l1), C1, ptr(w), w.shape[-1], ptr(out), Cout, nimg, H, W, ptr(acc_scale), stream())
+    return out
+
+
+def conv_wgrad(gy, ldg, xp, Cout, Cin, nimg, H, W, gy_scale, x_scale, dw=None):
+    """mk_conv_wgrad: gy / xp = (hi, lo) plane views (conv_train_plane_buffer) of gY [.., ldg] and X [.., Cin] -> dw fp32
+    [Cout, Cin, 3, 3]."""
+    if dw is None:
+        dw = torch.empty((Cout, Cin, 3, 3), device=xp[0].device, dtype=torch.float32)
+    assert dw.dtype == torch.float32 and dw.is_contiguous() and tuple(dw.shape) == (Cout, Cin, 3, 3)
+    work = torch.empty(max(1, int(query("mk_conv_wgrad_work_floats", Cout, Cin, nimg, H, W))), device=dw.device, dtype=torch.float32)
+    call("mk_conv_wgrad", ptr(gy[0]), ptr(gy[1]), ldg, ptr(xp[0]), ptr(xp[1]), Cout, Cin, nimg, H, W, ptr(gy_scale), ptr(x_scale),
+         ptr(work), ptr(dw), stream())
+    return dw
+
+
 def posenc_add(x, pe, xs, cat, groups, nimg, npix, C):
     call("mk_posenc_add", ptr(x), ptr(pe), ptr(xs), ptr(cat), cat.stride(-2), groups, nimg, npix, C, dtype_code(x.dtype),
          stream())
