@@ -320,6 +320,33 @@ int mk_linattn_kv(const float* qkv, float* kv, float* work, int groups, int nimg
 int mk_linattn_apply(const float* qkv, const float* kv, void* out, int ldo, int groups, int nimg, int L, int C, int dtype,
                      mk_stream_t stream);
 
+/* The same linear attention for TRAINING (att_layers/attention.py:46-64 under autograd), forward and backward, all fp32.
+ * Per image n and head h (16 channels), phi(x) = elu(x) + 1, phi'(x) = 1 for x > 0, else phi(x):
+ *   forward   M[d, v] = sum_s phi(k)[s, d] (v[s, v] / S),  ks[d] = sum_s phi(k)[s, d]
+ *             den[l] = phi(q)[l] . ks + eps,  out[l, v] = (phi(q)[l] . M[:, v]) / den[l] * S
+ *   backward  gnum[l, v] = go[l, v] S / den[l],  gden[l] = -(go[l] . out[l]) / den[l]      (out and den recomputed from q, M, ks)
+ *             gq[l, d] = (sum_v gnum[l, v] M[d, v] + gden[l] ks[d]) phi'(q[l, d])
+ *             gM[d, v] = sum_l phi(q)[l, d] gnum[l, v],  gks[d] = sum_l phi(q)[l, d] gden[l]
+ *             gk[s, d] = (sum_v (v[s, v] / S) gM[d, v] + gks[d]) phi'(k[s, d]),  gv[s, v] = (sum_d phi(k)[s, d] gM[d, v]) / S
+ * q [nimg][L rows], k, v [nimg][S rows]: three separate fp32 operands of C = 16 H channels per row, each with its own row stride
+ * (ld*, elements, >= C) and image stride (s*, elements); pointers 16-byte aligned, strides multiples of 4.  L and S may differ.
+ *   out  fp32 [nimg * L, C] dense
+ *   kv   fp32 [nimg * (C / 16)][272]: M (16 x 16, d-major) | ks per (image, head), the layout of mk_linattn_kv; written by the
+ *        forward, read by the backward (what a caller keeps between the two, besides q, k and v)
+ *   go   fp32 [nimg * L, C] dense;  gq [nimg * L, C], gk, gv [nimg * S, C] dense, each may be NULL (not wanted: not computed)
+ *   gkv  fp32 [nimg * (C / 16)][272] scratch (gM | gks), work: mk_linattn_train_work_floats(nimg, L, S, C) fp32 elements; both
+ *        may be NULL when gk and gv are
+ * Both token sums are deterministic: per-chunk partials in `work`, added in chunk order, no atomics; an image's results do not
+ * depend on the other images of the call.  3 launches forward; backward 3, or 1 when neither gk nor gv is wanted.
+ * eps is a per-call argument.  C % 16 == 0, C <= 128, nimg <= 65535. */
+long long mk_linattn_train_work_floats(int nimg, int L, int S, int C);
+int mk_linattn_train_fwd(const float* q, long long ldq, long long sq, const float* k, long long ldk, long long sk, const float* v,
+                         long long ldv, long long sv, float eps, float* out, float* kv, float* work, int nimg, int L, int S, int C,
+                         mk_stream_t stream);
+int mk_linattn_train_bwd(const float* q, long long ldq, long long sq, const float* k, long long ldk, long long sk, const float* v,
+                         long long ldv, long long sv, const float* kv, const float* go, float eps, float* work, float* gkv, float* gq,
+                         float* gk, float* gv, int nimg, int L, int S, int C, mk_stream_t stream);
+
 /* Head tails (mickey_extractor.py:134-138,173-176,213-216,246-249 and
  * compute_correspondences.py:20-31).  feat* fp32 [nimg*h*w, C] (resblock4 outputs).
  *   scr   [nimg, h*w]      border-masked temperature-100 softmax (or sigmoid) of w_score . feat_det

@@ -57,6 +57,9 @@ SIGNATURES = {
     "mk_linattn_work_floats": ("l", "iiii"),
     "mk_linattn_kv": ("i", "pppiiiip"),
     "mk_linattn_apply": ("i", "pppiiiiiip"),
+    "mk_linattn_train_work_floats": ("l", "iiii"),
+    "mk_linattn_train_fwd": ("i", "pllpllpllfpppiiiip"),
+    "mk_linattn_train_bwd": ("i", "pllpllpllppfpppppiiiip"),
     "mk_head_tails": ("i", "pppppppppppiiiiiiiififp"),
     "mk_dual_softmax_work_floats": ("l", "iiii"),
     "mk_dual_softmax": ("i", "ppppfifppppiiiip"),

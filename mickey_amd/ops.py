@@ -401,6 +401,46 @@ def linattn_apply(qkv, kv, out, ldo, groups, nimg, L, C):
     call("mk_linattn_apply", ptr(qkv), ptr(kv), ptr(out), ldo, groups, nimg, L, C, dtype_code(out.dtype), stream())
 
 
+# ---- training: the heads' linear attention (mickey_hip.h: mk_linattn_train_*; train_attention.py) ------------------------------
+def _attn_rows(t):
+    """[N, T, H, 16] fp32 device tensor with dense last two dimensions -> (pointer, row stride, image stride); the stride of a
+    dimension of size 1 means nothing and is replaced by the dense one."""
+    N, T, H, D = t.shape
+    assert t.dtype == torch.float32 and D == 16 and t.stride(3) == 1 and (H == 1 or t.stride(2) == 16)
+    ld = t.stride(1) if T > 1 else H * 16
+    return ptr(t), ld, t.stride(0) if N > 1 else T * ld
+
+
+def linattn_train_fwd(q, k, v, eps):
+    """mk_linattn_train_fwd: q [N, L, H, 16], k, v [N, S, H, 16] (rows of any stride) -> (out [N, L, H, 16] contiguous,
+    kv [N * H, 272]: the M | ks block the backward reads)."""
+    N, L, H, _ = q.shape
+    S, C = k.shape[1], H * 16
+    out = torch.empty((N, L, H, 16), device=q.device, dtype=torch.float32)
+    kv = torch.empty((N * H, 272), device=q.device, dtype=torch.float32)
+    work = torch.empty(int(query("mk_linattn_train_work_floats", N, L, S, C)), device=q.device, dtype=torch.float32)
+    call("mk_linattn_train_fwd", *_attn_rows(q), *_attn_rows(k), *_attn_rows(v), float(eps), ptr(out), ptr(kv), ptr(work), N, L, S, C,
+         stream())
+    return out, kv
+
+
+def linattn_train_bwd(q, k, v, kv, go, eps, need):
+    """mk_linattn_train_bwd: go [N, L, H, 16] contiguous, need = (gq, gk, gv wanted) -> (gq, gk, gv), None where not wanted."""
+    N, L, H, _ = q.shape
+    S, C = k.shape[1], H * 16
+    assert go.dtype == torch.float32 and go.is_contiguous() and tuple(go.shape) == (N, L, H, 16) and tuple(kv.shape) == (N * H, 272)
+    gq = torch.empty((N, L, H, 16), device=q.device, dtype=torch.float32) if need[0] else None
+    gk = torch.empty((N, S, H, 16), device=q.device, dtype=torch.float32) if need[1] else None
+    gv = torch.empty((N, S, H, 16), device=q.device, dtype=torch.float32) if need[2] else None
+    work = gkv = None
+    if need[1] or need[2]:
+        gkv = torch.empty((N * H, 272), device=q.device, dtype=torch.float32)
+        work = torch.empty(int(query("mk_linattn_train_work_floats", N, L, S, C)), device=q.device, dtype=torch.float32)
+    call("mk_linattn_train_bwd", *_attn_rows(q), *_attn_rows(k), *_attn_rows(v), ptr(kv), ptr(go), float(eps), ptr(work), ptr(gkv),
+         ptr(gq), ptr(gk), ptr(gv), N, L, S, C, stream())
+    return gq, gk, gv
+
+
 def head_tails(f_det, w_score, f_off, w_xy, f_dep, w_dep, f_dsc, nimg, h, w, C, Cd, border=3, use_softmax=True,
                use_depth_sigmoid=False, max_depth=60.0, norm_dsc=True, down=14.0):
     dev = f_det.device
