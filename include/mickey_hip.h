@@ -320,6 +320,21 @@ int mk_linattn_kv(const float* qkv, float* kv, float* work, int groups, int nimg
 int mk_linattn_apply(const float* qkv, const float* kv, void* out, int ldo, int groups, int nimg, int L, int C, int dtype,
                      mk_stream_t stream);
 
+/* Steps 1 and 2 with the projections inside (C = 128, 16-bit operands: the heads' default path).  x lp [G][nimg*L, lda] holds the
+ * layer's input rows (columns [0, C)), qkv_w lp [G][3C, ldw] the rows of q | k | v.  Nothing of q, k, v reaches memory.
+ * mk_linattn_kv_fused: kv and work exactly as mk_gemm_grouped (fp32 out) -> mk_linattn_kv leave them, bit for bit (the same
+ * accumulators, the same order of every sum).
+ * mk_linattn_apply_fused: with merge_w lp [G][C, ldwm] and ln_w / ln_b fp32 [G, C] the rows
+ *   LayerNorm_C(msg . merge_w^T) * ln_w + ln_b   (mk_gemm_grouped -> mk_linattn_apply -> mk_gemm_ln128, bit for bit)
+ * are written lp to out [G][nimg*L, ldo]; merge_w == NULL: out receives msg itself (mk_linattn_apply's rows).  out may be other
+ * columns of the rows x is read from.  x, qkv_w, merge_w, kv 16-byte aligned, out 8-byte aligned, strides in elements. */
+int mk_linattn_kv_fused(const void* x, int lda, long long strideX, const void* qkv_w, int ldw, long long strideW, float* kv,
+                        float* work, int groups, int nimg, int L, int C, int dtype, mk_stream_t stream);
+int mk_linattn_apply_fused(const void* x, int lda, long long strideX, const void* qkv_w, int ldw, long long strideW, const float* kv,
+                           const void* merge_w, int ldwm, long long strideWm, const float* ln_w, const float* ln_b, float eps,
+                           void* out, int ldo, long long strideOut, int groups, int nimg, int L, int C, int dtype,
+                           mk_stream_t stream);
+
 /* The same linear attention for TRAINING (att_layers/attention.py:46-64 under autograd), forward and backward, all fp32.
  * Per image n and head h (16 channels), phi(x) = elu(x) + 1, phi'(x) = 1 for x > 0, else phi(x):
  *   forward   M[d, v] = sum_s phi(k)[s, d] (v[s, v] / S),  ks[d] = sum_s phi(k)[s, d]

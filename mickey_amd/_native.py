@@ -57,6 +57,8 @@ SIGNATURES = {
     "mk_linattn_work_floats": ("l", "iiii"),
     "mk_linattn_kv": ("i", "pppiiiip"),
     "mk_linattn_apply": ("i", "pppiiiiiip"),
+    "mk_linattn_kv_fused": ("i", "pilpilppiiiiip"),
+    "mk_linattn_apply_fused": ("i", "pilpilppilppfpiliiiiip"),
     "mk_linattn_train_work_floats": ("l", "iiii"),
     "mk_linattn_train_fwd": ("i", "pllpllpllfpppiiiip"),
     "mk_linattn_train_bwd": ("i", "pllpllpllppfpppppiiiip"),

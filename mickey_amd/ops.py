@@ -401,6 +401,25 @@ def linattn_apply(qkv, kv, out, ldo, groups, nimg, L, C):
     call("mk_linattn_apply", ptr(qkv), ptr(kv), ptr(out), ldo, groups, nimg, L, C, dtype_code(out.dtype), stream())
 
 
+def linattn_kv_fused(x, qkv_w, kv, work, groups, nimg, L, C, lda=None):
+    """mk_linattn_kv_fused: kv / work as gemm_grouped(x, qkv_w) -> linattn_kv leave them, without the fp32 qkv rows.  x lp [G, nimg * L,
+    lda] (columns [0, C) are read), qkv_w lp [G, 3C, C]."""
+    lda = x.stride(-2) if lda is None else lda
+    call("mk_linattn_kv_fused", ptr(x), lda, x.stride(0), ptr(qkv_w), qkv_w.stride(-2), qkv_w.stride(0), ptr(kv), ptr(work), groups, nimg,
+         L, C, dtype_code(x.dtype), stream())
+
+
+def linattn_apply_fused(x, qkv_w, kv, out, groups, nimg, L, C, merge_w=None, ln_w=None, ln_b=None, eps=1e-5, lda=None):
+    """mk_linattn_apply_fused: q projection + linattn_apply, and with merge_w / ln_w / ln_b also merge -> norm1 (gemm_ln128), in one
+    launch.  out lp [G, nimg * L, ldo] (a view: its strides are passed on) receives the normalised rows, or msg without merge_w."""
+    lda = x.stride(-2) if lda is None else lda
+    mw = merge_w is not None
+    call("mk_linattn_apply_fused", ptr(x), lda, x.stride(0), ptr(qkv_w), qkv_w.stride(-2), qkv_w.stride(0), ptr(kv), ptr(merge_w),
+         merge_w.stride(-2) if mw else 0, merge_w.stride(0) if mw else 0, ptr(ln_w), ptr(ln_b), float(eps), ptr(out), out.stride(-2),
+         out.stride(0), groups, nimg, L, C, dtype_code(x.dtype), stream())
+    return out
+
+
 # ---- training: the heads' linear attention (mickey_hip.h: mk_linattn_train_*; train_attention.py) ------------------------------
 def _attn_rows(t):
     """[N, T, H, 16] fp32 device tensor with dense last two dimensions -> (pointer, row stride, image stride); the stride of a

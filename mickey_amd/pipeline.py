@@ -204,10 +204,14 @@ def heads_forward(W, ws, feat, nimg, gh, gw, cfg):
     else:
         ops.posenc_add(x_in[:3], pe if kp_pe else None, xs[:3], cat[:3], 3, nimg, n, C)
         ops.posenc_add(x_in[3:], pe if dsc_pe else None, xs[3:], cat[3:], 1, nimg, n, C)
-    qkv = ws.get("att_qkv", (G, M, 3 * C), torch.float32, dev)
+    # AMD.LINATTN_FUSED: q | k | v are projected inside the attention kernels (mk_linattn_*_fused: C = 128, 16-bit operands) -- no
+    # fp32 qkv rows, no msg rows; off = the separate launches (the same results bit for bit, for A/B runs)
+    fused_att = bool(cfg["AMD"].get("LINATTN_FUSED", True)) and not split and C == 128 and lp != torch.float32
     kv = ws.get("att_kv", (G * nimg * (C // 16), 272), torch.float32, dev)
     kvw = ws.get("att_kvw", (ops.linattn_work_floats(G, nimg, n, C),), torch.float32, dev)
-    msg = ws.get("att_msg", (G, M, C), lp, dev)
+    if not fused_att:
+        qkv = ws.get("att_qkv", (G, M, 3 * C), torch.float32, dev)
+        msg = ws.get("att_msg", (G, M, C), lp, dev)
     mrg = ws.get("att_mrg", (G, M, C), torch.float32, dev)
     hid = ws.get("att_hid", (G, M, 2 * C), lp, dev)
     if split:
@@ -240,6 +244,11 @@ def heads_forward(W, ws, feat, nimg, gh, gw, cfg):
                                    M * 2 * C, act=ops.ACT_RELU, w_scale=wsc(lay.mlp0_w), sat=sat)
             ops.gemm_grouped_split(hidp, lay.mlp2_w, None, mrg, G, M, C, 2 * C, 2 * C, C, M * 2 * C, C * 2 * 2 * C, 0, M * C,
                                    w_scale=wsc(lay.mlp2_w), sat=sat)
+        elif fused_att:
+            ops.linattn_kv_fused(cat, lay.qkv_w, kv, kvw, G, nimg, n, C)
+            ops.linattn_apply_fused(cat, lay.qkv_w, kv, cat[:, :, C:], G, nimg, n, C, merge_w=lay.merge_w, ln_w=lay.n1w, ln_b=lay.n1b)
+            ops.gemm_grouped(cat, lay.mlp0_w, None, hid, G, M, 2 * C, 2 * C, 2 * C, 2 * C, 2 * C, M * 2 * C, 4 * C * C, 0,
+                             M * 2 * C, act=ops.ACT_RELU)
         else:
             ops.gemm_grouped(cat, lay.qkv_w, None, qkv, G, M, 3 * C, C, 2 * C, C, 3 * C, M * 2 * C, 3 * C * C, 0, M * 3 * C)
             ops.linattn_kv(qkv, kv, kvw, G, nimg, n, C)
