@@ -362,6 +362,60 @@ int mk_linattn_train_bwd(const float* q, long long ldq, long long sq, const floa
                          long long ldv, long long sv, const float* kv, const float* go, float eps, float* work, float* gkv, float* gq,
                          float* gk, float* gv, int nimg, int L, int S, int C, mk_stream_t stream);
 
+/* The rest of the heads' EncoderLayer for TRAINING (att_layers/transformer_utils.py:40-66 under autograd): its bias-free
+ * nn.Linears and its two LayerNorm(128), forward and backward, all fp32.  Contractions on the fp32-input MFMA (an exact fp32 fma
+ * chain) in an order fixed by the shape: bit-identical from run to run, a row of a forward / input-gradient result does not depend
+ * on the other rows, gradients are bit-linear in the incoming gradient under a power-of-two scale; no atomics, no host sync.
+ * All pointers 16-byte aligned, all row strides (elements) multiples of 4 and >= the row's width.
+ *
+ * mk_train_linear_fwd (transformer_utils.py:55-57,59,63: q_proj / k_proj / v_proj, merge, mlp[0] + ReLU on the concat, mlp[2]):
+ *   out[M, N] = act([A1 | A2] . W^T),  A1 [M, K1], A2 [M, K2] (K2 == 0: one source), W [N, K1 + K2] dense in nn.Linear's layout;
+ *   relu != 0: act = max(., 0) (a NaN stays a NaN).  wsplit != 0: W is three dense matrices w | w2 | w3 of wsplit rows each
+ *   (N == 3 wsplit; wq | wk | wv read where they lie).  K1, K2 multiples of 16, N of 4.
+ * mk_train_linear_ln128_fwd (transformer_utils.py:59-60 and 63-66: merge + norm1, mlp[2] + norm2 + the residual, one pass):
+ *   out[M, 128] = LayerNorm_128([A1 | A2] . W^T) gamma + beta (+ resid), the row statistics taken in the accumulators; xhat [M, 128]
+ *   and rstd [M] (either may be NULL) as mk_train_ln128_fwd leaves them (another summation order: not the same bits).
+ * mk_train_linear_dgrad (the input gradient of the same Linears):
+ *   [o1 | o2][M, K1 + K2] (+)= (G[M, N] . W[N, K1 + K2]) with an exact zero wherever mask[m, j] <= 0 (mask NULL: none; mlp[1]'s ReLU
+ *   backward behind mlp[2]'s input gradient).  Columns [0, K1) go to o1, [K1, K1 + K2) to o2 (mlp[0]'s gradient lands as gx and gm
+ *   without a split); accumulate bit 0 / bit 1 adds to what o1 / o2 holds (one writer per element).  N a multiple of 16, K1, K2 of 4.
+ *   gsplit != 0: G lies as N / gsplit planes of gsplit columns, gplane elements apart, rows ldg apart (gq | gk | gv as
+ *   mk_linattn_train_bwd leaves them; gsplit a multiple of 16); the same for mk_train_linear_wgrad.
+ * mk_train_linear_wgrad (the weight gradient):
+ *   part[c * chunk_stride + n (K1 + K2) + k] = sum over the rows m of chunk c of G[m, n] [A1 | A2][m, k],  c < chunks; chunk c is
+ *   rows [c rows_per_chunk, (c + 1) rows_per_chunk) (a chunk past M gets zeros).  mk_train_rows_per_chunk(M) / mk_train_chunks(M)
+ *   give the chunking of an M-row call: whole steps of 128 rows, at most 32 chunks, a function of M alone.
+ * mk_train_tail (one launch for every partial sum of a backward pass):
+ *   out[j] = sum_c wpart[c wstride + j], j < nw, and out[nw + j] = sum_s lpart[s lstride + j], j < nl, both in index order.
+ * mk_train_ln128_fwd (transformer_utils.py:60,64,66: norm1, norm2 and the residual):
+ *   xhat = (u - mean) rstd, out = xhat gamma + beta (+ resid), rows of 128; xhat [M, 128] and rstd [M] (either may be NULL) are what
+ *   the backward needs.
+ * mk_train_ln128_bwd:
+ *   gu = rstd (gamma g - mean(gamma g) - xhat mean(gamma g xhat)) (gu NULL: not wanted), and per step s of 128 rows
+ *   part[s part_stride + 0..127] = sum_m g xhat (gamma's gradient), part[s part_stride + 128..255] = sum_m g (beta's); part NULL:
+ *   not wanted.  mk_train_ln_steps(M) steps. */
+int mk_train_rows_per_chunk(int M);
+int mk_train_chunks(int M);
+int mk_train_ln_steps(int M);
+int mk_train_linear_fwd(const float* a1, long long lda1, int K1, const float* a2, long long lda2, int K2, const float* w,
+                        const float* w2, const float* w3, int wsplit, float* out, long long ldo, int M, int N, int relu,
+                        mk_stream_t stream);
+int mk_train_linear_ln128_fwd(const float* a1, long long lda1, int K1, const float* a2, long long lda2, int K2, const float* w,
+                              const float* gamma, const float* beta, float eps, const float* resid, long long ldr, float* out,
+                              float* xhat, float* rstd, int M, mk_stream_t stream);
+int mk_train_linear_dgrad(const float* g, long long ldg, long long gplane, int gsplit, const float* w, const float* w2, const float* w3, int wsplit,
+                          const float* mask, long long ldmask, float* o1, long long ldo1, int K1, float* o2, long long ldo2, int K2,
+                          int accumulate, int M, int N, mk_stream_t stream);
+int mk_train_linear_wgrad(const float* g, long long ldg, long long gplane, int gsplit, const float* a1, long long lda1, int K1, const float* a2, long long lda2,
+                          int K2, float* part, long long chunk_stride, int rows_per_chunk, int chunks, int M, int N,
+                          mk_stream_t stream);
+int mk_train_tail(const float* wpart, long long wstride, int wchunks, long long nw, const float* lpart, long long lstride,
+                  int lsteps, long long nl, float* out, mk_stream_t stream);
+int mk_train_ln128_fwd(const float* u, const float* gamma, const float* beta, float eps, const float* resid, long long ldr,
+                       float* out, float* xhat, float* rstd, int M, mk_stream_t stream);
+int mk_train_ln128_bwd(const float* g, const float* xhat, const float* rstd, const float* gamma, float* gu, float* part,
+                       long long part_stride, int M, mk_stream_t stream);
+
 /* Head tails (mickey_extractor.py:134-138,173-176,213-216,246-249 and
  * compute_correspondences.py:20-31).  feat* fp32 [nimg*h*w, C] (resblock4 outputs).
  *   scr   [nimg, h*w]      border-masked temperature-100 softmax (or sigmoid) of w_score . feat_det

@@ -62,6 +62,16 @@ SIGNATURES = {
     "mk_linattn_train_work_floats": ("l", "iiii"),
     "mk_linattn_train_fwd": ("i", "pllpllpllfpppiiiip"),
     "mk_linattn_train_bwd": ("i", "pllpllpllppfpppppiiiip"),
+    "mk_train_rows_per_chunk": ("i", "i"),
+    "mk_train_chunks": ("i", "i"),
+    "mk_train_ln_steps": ("i", "i"),
+    "mk_train_linear_fwd": ("i", "pliplipppipliiip"),
+    "mk_train_linear_ln128_fwd": ("i", "pliplipppfplpppip"),
+    "mk_train_linear_dgrad": ("i", "pllipppiplplipliiiip"),
+    "mk_train_linear_wgrad": ("i", "pllipliplipliiiip"),
+    "mk_train_tail": ("i", "plilplilpp"),
+    "mk_train_ln128_fwd": ("i", "pppfplpppip"),
+    "mk_train_ln128_bwd": ("i", "pppppplip"),
     "mk_head_tails": ("i", "pppppppppppiiiiiiiififp"),
     "mk_dual_softmax_work_floats": ("l", "iiii"),
     "mk_dual_softmax": ("i", "ppppfifppppiiiip"),

@@ -443,14 +443,18 @@ def linattn_train_fwd(q, k, v, eps):
     return out, kv
 
 
-def linattn_train_bwd(q, k, v, kv, go, eps, need):
-    """mk_linattn_train_bwd: go [N, L, H, 16] contiguous, need = (gq, gk, gv wanted) -> (gq, gk, gv), None where not wanted."""
+def linattn_train_bwd(q, k, v, kv, go, eps, need, out=None):
+    """mk_linattn_train_bwd: go [N, L, H, 16] contiguous, need = (gq, gk, gv wanted) -> (gq, gk, gv), None where not wanted.
+    out: optional contiguous buffers (gq, gk, gv) to write instead of new ones (e.g. three planes of one allocation)."""
     N, L, H, _ = q.shape
     S, C = k.shape[1], H * 16
     assert go.dtype == torch.float32 and go.is_contiguous() and tuple(go.shape) == (N, L, H, 16) and tuple(kv.shape) == (N * H, 272)
-    gq = torch.empty((N, L, H, 16), device=q.device, dtype=torch.float32) if need[0] else None
-    gk = torch.empty((N, S, H, 16), device=q.device, dtype=torch.float32) if need[1] else None
-    gv = torch.empty((N, S, H, 16), device=q.device, dtype=torch.float32) if need[2] else None
+    if out is not None:
+        assert all(o.is_contiguous() and o.dtype == torch.float32 and o.numel() == N * T * C for o, T in zip(out, (L, S, S)))
+    new = lambda T, i: out[i] if out is not None else torch.empty((N, T, H, 16), device=q.device, dtype=torch.float32)   # noqa: E731
+    gq = new(L, 0) if need[0] else None
+    gk = new(S, 1) if need[1] else None
+    gv = new(S, 2) if need[2] else None
     work = gkv = None
     if need[1] or need[2]:
         gkv = torch.empty((N * H, 272), device=q.device, dtype=torch.float32)
@@ -458,6 +462,120 @@ def linattn_train_bwd(q, k, v, kv, go, eps, need):
     call("mk_linattn_train_bwd", *_attn_rows(q), *_attn_rows(k), *_attn_rows(v), ptr(kv), ptr(go), float(eps), ptr(work), ptr(gkv),
          ptr(gq), ptr(gk), ptr(gv), N, L, S, C, stream())
     return gq, gk, gv
+
+
+# ---- training: the Linears and LayerNorms of the heads' EncoderLayer (mickey_hip.h: mk_train_linear_* / mk_train_ln128_*;
+# train_layer.py).  Operands are 2-D fp32 device tensors whose rows are dense and 16-byte aligned (any row stride). ----------------
+def _mat(t):
+    """2-D fp32 tensor with dense rows -> (pointer, row stride); None -> (None, 0)."""
+    if t is None:
+        return None, 0
+    assert t.dtype == torch.float32 and t.dim() == 2 and (t.shape[1] == 1 or t.stride(1) == 1)
+    return ptr(t), (t.stride(0) if t.shape[0] > 1 else t.shape[1])
+
+
+def _wsplit(w):
+    """a weight, or a tuple of three equally shaped ones read as their row-wise concatenation -> (w, w2, w3, wsplit)"""
+    if isinstance(w, (tuple, list)):
+        a, b, c = w
+        assert a.shape == b.shape == c.shape and all(x.is_contiguous() and x.dtype == torch.float32 for x in w)
+        return ptr(a), ptr(b), ptr(c), a.shape[0]
+    assert w.is_contiguous() and w.dtype == torch.float32
+    return ptr(w), None, None, 0
+
+
+def _gplanes(g):
+    """a gradient [M, N], or planes [P, M, n] read as [M, P n] -> (pointer, row stride, plane stride, columns per plane, M, N)"""
+    if g.dim() == 3:
+        P, M, n = g.shape
+        assert g.dtype == torch.float32 and g.stride(2) == 1
+        return ptr(g), (g.stride(1) if M > 1 else n), (g.stride(0) if P > 1 else 0), n, M, P * n
+    p, ld = _mat(g)
+    return p, ld, 0, 0, g.shape[0], g.shape[1]
+
+
+def train_chunks(M):
+    """(rows per chunk, chunks) of an M-row weight gradient: a function of M alone."""
+    return int(query("mk_train_rows_per_chunk", M)), int(query("mk_train_chunks", M))
+
+
+def train_ln_steps(M):
+    return int(query("mk_train_ln_steps", M))
+
+
+def train_linear_fwd(a1, w, a2=None, relu=False, out=None):
+    """mk_train_linear_fwd: out [M, N] = act([a1 | a2] . w^T); w [N, K1 + K2] or a tuple of three such matrices (rows concatenated)."""
+    M, K1 = a1.shape
+    K2 = 0 if a2 is None else a2.shape[1]
+    pw, pw2, pw3, ws = _wsplit(w)
+    N = 3 * ws if ws else w.shape[0]
+    if out is None:
+        out = torch.empty((M, N), device=a1.device, dtype=torch.float32)
+    call("mk_train_linear_fwd", *_mat(a1), K1, *_mat(a2), K2, pw, pw2, pw3, ws, *_mat(out), M, N, int(bool(relu)), stream())
+    return out
+
+
+def train_linear_ln128_fwd(a1, w, gamma, beta, eps, a2=None, resid=None, want_saved=True):
+    """mk_train_linear_ln128_fwd: LayerNorm_128([a1 | a2] . w^T) gamma + beta (+ resid) -> (out, xhat, rstd); xhat and rstd are None
+    unless want_saved."""
+    M, K1 = a1.shape
+    K2 = 0 if a2 is None else a2.shape[1]
+    assert w.is_contiguous() and tuple(w.shape) == (128, K1 + K2) and gamma.is_contiguous() and beta.is_contiguous()
+    out = torch.empty((M, 128), device=a1.device, dtype=torch.float32)
+    xhat = torch.empty_like(out) if want_saved else None
+    rstd = torch.empty((M,), device=a1.device, dtype=torch.float32) if want_saved else None
+    call("mk_train_linear_ln128_fwd", *_mat(a1), K1, *_mat(a2), K2, ptr(w), ptr(gamma), ptr(beta), float(eps), *_mat(resid), ptr(out),
+         ptr(xhat), ptr(rstd), M, stream())
+    return out, xhat, rstd
+
+
+def train_linear_dgrad(g, w, o1, o2=None, mask=None, accumulate=0):
+    """mk_train_linear_dgrad: [o1 | o2] (+)= (g . w), zero where mask <= 0.  g [M, N] or planes [P, M, N / P]; accumulate: bit 0 adds
+    to o1, bit 1 to o2."""
+    pg, ldg, gplane, gsplit, M, N = _gplanes(g)
+    pw, pw2, pw3, ws = _wsplit(w)
+    K1 = o1.shape[1]
+    K2 = 0 if o2 is None else o2.shape[1]
+    call("mk_train_linear_dgrad", pg, ldg, gplane, gsplit, pw, pw2, pw3, ws, *_mat(mask), *_mat(o1), K1, *_mat(o2), K2,
+         int(accumulate), M, N, stream())
+
+
+def train_linear_wgrad(g, a1, part, chunk_stride, rows_per_chunk, chunks, a2=None):
+    """mk_train_linear_wgrad: per-chunk partials of g^T . [a1 | a2] into part (a 1-D view whose element 0 is chunk 0's [N, K])."""
+    pg, ldg, gplane, gsplit, M, N = _gplanes(g)
+    K1 = a1.shape[1]
+    K2 = 0 if a2 is None else a2.shape[1]
+    assert part.dtype == torch.float32 and part.is_contiguous() and part.numel() >= (chunks - 1) * chunk_stride + N * (K1 + K2)
+    call("mk_train_linear_wgrad", pg, ldg, gplane, gsplit, *_mat(a1), K1, *_mat(a2), K2, ptr(part), chunk_stride, rows_per_chunk, chunks,
+         M, N, stream())
+
+
+def train_tail(wpart, wstride, wchunks, nw, lpart, lstride, lsteps, nl, out):
+    """mk_train_tail: every chunk / step partial of a backward pass -> out [nw + nl], added in index order, one launch."""
+    assert out.is_contiguous() and out.numel() >= nw + nl
+    assert nw == 0 or wpart.numel() >= (wchunks - 1) * wstride + nw
+    assert nl == 0 or lpart.numel() >= (lsteps - 1) * lstride + nl
+    call("mk_train_tail", ptr(wpart) if nw else None, wstride, wchunks, nw, ptr(lpart) if nl else None, lstride, lsteps, nl, ptr(out),
+         stream())
+
+
+def train_ln128_fwd(u, gamma, beta, eps, resid=None, want_saved=True):
+    """mk_train_ln128_fwd: u [M, 128] dense -> (out, xhat, rstd); xhat and rstd are None unless want_saved."""
+    M = u.shape[0]
+    assert u.is_contiguous() and u.shape[1] == 128 and gamma.is_contiguous() and beta.is_contiguous()
+    out = torch.empty_like(u)
+    xhat = torch.empty_like(u) if want_saved else None
+    rstd = torch.empty((M,), device=u.device, dtype=torch.float32) if want_saved else None
+    call("mk_train_ln128_fwd", ptr(u), ptr(gamma), ptr(beta), float(eps), *_mat(resid), ptr(out), ptr(xhat), ptr(rstd), M, stream())
+    return out, xhat, rstd
+
+
+def train_ln128_bwd(g, xhat, rstd, gamma, gu=None, part=None, part_stride=256):
+    """mk_train_ln128_bwd: gu [M, 128] (None: not wanted) and the per-step column sums g xhat | g into part (None: not wanted)."""
+    M = g.shape[0]
+    assert g.is_contiguous() and xhat.is_contiguous() and g.shape[1] == 128 and (gu is None or gu.is_contiguous())
+    assert part is None or part.numel() >= (train_ln_steps(M) - 1) * part_stride + 256
+    call("mk_train_ln128_bwd", ptr(g), ptr(xhat), ptr(rstd), ptr(gamma), ptr(gu), ptr(part), part_stride, M, stream())
 
 
 def head_tails(f_det, w_score, f_off, w_xy, f_dep, w_dep, f_dsc, nimg, h, w, C, Cd, border=3, use_softmax=True,

@@ -23,8 +23,8 @@ value computed from it.
     use_hip_attention(model)                swaps it into a reference-style model in place (next to use_hip_matcher /
                                             use_hip_encoder / use_hip_convs)
 
-Not covered: the q / k / v / merge / MLP nn.Linears and the LayerNorms of EncoderLayer, BatchNorm, ReLU and the 1x1 convolutions
-(they stay in torch); autocast and half-precision inputs (ValueError); double backward; head sizes other than 16; hipGraph capture
+Not covered here: the q / k / v / merge / MLP nn.Linears and the LayerNorms of EncoderLayer (train_layer.py runs the whole layer
+around this core as one node); BatchNorm, ReLU and the 1x1 convolutions (they stay in torch); autocast and half-precision inputs (ValueError); double backward; head sizes other than 16; hipGraph capture
 of a step.
 """
 import math
