@@ -384,6 +384,7 @@ def conv_wgrad(gy, ldg, xp, Cout, Cin, nimg, H, W, gy_scale, x_scale, dw=None):
     return dw
 
 
+# ---- the heads' positional encoding (mk_heads.hip) and linear attention for inference (mickey_hip.h: mk_linattn_*; mk_linattn.hip) ----
 def posenc_add(x, pe, xs, cat, groups, nimg, npix, C):
     call("mk_posenc_add", ptr(x), ptr(pe), ptr(xs), ptr(cat), cat.stride(-2), groups, nimg, npix, C, dtype_code(x.dtype),
          stream())
@@ -420,7 +421,8 @@ def linattn_apply_fused(x, qkv_w, kv, out, groups, nimg, L, C, merge_w=None, ln_
     return out
 
 
-# ---- training: the heads' linear attention (mickey_hip.h: mk_linattn_train_*; train_attention.py) ------------------------------
+# ---- training: the heads' linear attention (mickey_hip.h: mk_linattn_train_*, mk_linattn.hip beside the inference kernels;
+# train_attention.py) ------------------------------------------------------------------------------------------------------------
 def _attn_rows(t):
     """[N, T, H, 16] fp32 device tensor with dense last two dimensions -> (pointer, row stride, image stride); the stride of a
     dimension of size 1 means nothing and is replaced by the dense one."""

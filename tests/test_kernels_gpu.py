@@ -1051,22 +1051,41 @@ def test_gemm_ln128_equals_gemm_then_layernorm(K, with_resid, bordered, nimg, H,
     assert rel(out_b.float(), y) < (6e-4 if dtype == torch.float16 else 5e-3)
 
 
-def test_linear_attention_and_posenc():
+def _check_linear_attention(h, w, C, dtype):
+    """mk_linattn_kv + mk_linattn_apply (the unfused kernels, KV_CHUNK = 64 tokens per partial block) against the oracle"""
     from mickey_amd import ops
     from oracle import mickey_oracle as O
     dev = _dev()
-    G, nimg, h, w, C = 2, 2, 9, 7, 128
+    G, nimg = 2, 2
     L = h * w
     qkv = torch.randn((G, nimg * L, 3 * C), generator=g(1))
     qd = qkv.to(dev)
     kv = torch.empty((G * nimg * (C // 16), 272), device=dev)
     work = torch.empty((ops.linattn_work_floats(G, nimg, L, C),), device=dev)
     ops.linattn_kv(qd, kv, work, G, nimg, L, C)
-    out = torch.empty((G, nimg * L, C), device=dev, dtype=torch.bfloat16)
+    out = torch.empty((G, nimg * L, C), device=dev, dtype=dtype)
     ops.linattn_apply(qd, kv, out, C, G, nimg, L, C)
-    x = qkv.reshape(G * nimg, L, 3, 8, 16)
+    x = qkv.reshape(G * nimg, L, 3, C // 16, 16)
     ref = O.linear_attention(x[:, :, 0], x[:, :, 1], x[:, :, 2]).reshape(G, nimg * L, C)
     assert rel(out.float(), ref) < 4e-3
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16], ids=["bf16", "fp16"])
+@pytest.mark.parametrize("C", [64, 128])
+@pytest.mark.parametrize("h,w", [(1, 1), (8, 8), (5, 13)])
+def test_linear_attention_chunk_edges(h, w, C, dtype):
+    """L = 1: one token, three idle waves; 64: exactly one chunk; 65: a second chunk of one token (L = 63 at C = 128 in bf16:
+    test_linear_attention_and_posenc)"""
+    _check_linear_attention(h, w, C, dtype)
+
+
+def test_linear_attention_and_posenc():
+    from mickey_amd import ops
+    from oracle import mickey_oracle as O
+    dev = _dev()
+    G, nimg, h, w, C = 2, 2, 9, 7, 128
+    L = h * w
+    _check_linear_attention(h, w, C, torch.bfloat16)
     # positional encoding add
     xin = torch.randn((G, nimg * L, C), generator=g(2)).bfloat16()
     pe = O.sine_pos_encoding(C, h, w).reshape(C, L).t().contiguous()
