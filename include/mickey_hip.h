@@ -528,7 +528,7 @@ int mk_mutual_nn(const float* scores, int* matches, int* count, int* work, int B
  *   noise  NULL: the race is drawn on device from Philox4x32-10(seed, offset) -- not cell by cell: with the threshold T of the
  *          keys known from the histogram of p, the candidates {p / e > T} of a row are generated directly as a thinned
  *          Bernoulli process (geometric skipping under a per-16-cell bound of p, acceptance s / S, e drawn from Exp(1)
- *          conditioned on e < p / T; mk_solver.hip), the same law as drawing every e; else fp32 [B*rows_per_pair, ncell]
+ *          conditioned on e < p / T; mk_sampler.hip), the same law as drawing every e; else fp32 [B*rows_per_pair, ncell]
  *          injected Exp(1) draws (tests: bit-comparable with torch)
  *   idx    int32 [B*rows_per_pair, k];  cnt int32 [B*rows_per_pair] = number of non-zero-key entries
  *          actually available (< k only if fewer than k cells have p > 0; the tail is then filled

@@ -20,7 +20,10 @@
 // (the 1 / (s_i^2 - s_j^2) poles of the separate U and V differentials cancel: unlike torch.svd's backward this stays finite
 // for equal singular values).  With Q = V^T (dL/dR) U:  dL/dH = U C V^T,
 //     C_ij = -(Q_ij - Q_ji) / (s_i + s_j)   resp.   C_i3 = C_3i = (Q_i3 + Q_3i) / (s_i - s_3)  when d = -1.
+// The rigid-fit arithmetic (Jacobi sweeps, column completion, Procrustes moments, 3x3 products) is mk_procrustes.hpp, shared with
+// mk_solver.hip; this file sets no contraction pragma, so here it compiles fused (see the head of that header).
 #include "mk_common.hpp"
+#include "mk_procrustes.hpp"
 
 namespace {
 using namespace mk;
@@ -43,84 +46,21 @@ struct TailParams {
   float img_h;           // clip bound of the projected eye points (720, metrics.py:70)
 };
 
-// ---- small fp64 3x3 helpers (row-major) ------------------------------------------------------------------------------
-__device__ __forceinline__ double det3(const double* M) {
-  return M[0] * (M[4] * M[8] - M[5] * M[7]) - M[1] * (M[3] * M[8] - M[5] * M[6]) + M[2] * (M[3] * M[7] - M[4] * M[6]);
-}
-
 // H = U diag(S) V^T, S descending, by one-sided Jacobi on the columns of H (G = H V has orthogonal columns = U S).
-// A vanishing third singular direction is completed by the cross product (sign from the column itself when it is resolvable).
+// U columns: normalised G columns, re-orthogonalised (Gram-Schmidt) so that tiny singular values do not leak noise.  A vanishing
+// third singular direction is completed by the cross product (sign from the column itself when it is resolvable).
+struct SvdFloor { static __device__ constexpr double value() { return 1e-300; } };
 __device__ void svd3(const double* Hin, double* U, double* S, double* V) {
-  double G[9], W[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+  double G[9], W[9], u0[3], u1[3], u2[3];
+  int ord[3];
+  jacobi_sweeps<15>(Hin, G, W, SvdFloor());
+  leading_pair(G, ord, S, u0, u1);
 #pragma unroll
-  for (int i = 0; i < 9; ++i) G[i] = Hin[i];
-  for (int sweep = 0; sweep < 15; ++sweep) {
-    double off = 0.0;
-#pragma unroll
-    for (int pq = 0; pq < 3; ++pq) {
-      const int p = pq == 2 ? 1 : 0, q = pq == 0 ? 1 : 2;
-      double al = 0, be = 0, ga = 0;
-#pragma unroll
-      for (int r = 0; r < 3; ++r) {
-        al += G[r * 3 + p] * G[r * 3 + p];
-        be += G[r * 3 + q] * G[r * 3 + q];
-        ga += G[r * 3 + p] * G[r * 3 + q];
-      }
-      if (fabs(ga) <= 1e-300 || ga * ga <= 1e-32 * al * be) continue;
-      off += fabs(ga);
-      const double zeta = (be - al) / (2.0 * ga);
-      const double tt = (zeta >= 0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
-      const double cs = 1.0 / sqrt(1.0 + tt * tt), sn = cs * tt;
-#pragma unroll
-      for (int r = 0; r < 3; ++r) {
-        const double gp = G[r * 3 + p], gq = G[r * 3 + q];
-        G[r * 3 + p] = cs * gp - sn * gq;
-        G[r * 3 + q] = sn * gp + cs * gq;
-        const double vp = W[r * 3 + p], vq = W[r * 3 + q];
-        W[r * 3 + p] = cs * vp - sn * vq;
-        W[r * 3 + q] = sn * vp + cs * vq;
-      }
-    }
-    if (off == 0.0) break;
-  }
-  double nrm[3];
-#pragma unroll
-  for (int c = 0; c < 3; ++c) nrm[c] = G[c] * G[c] + G[3 + c] * G[3 + c] + G[6 + c] * G[6 + c];
-  int o0 = 0, o1 = 1, o2 = 2;
-  if (nrm[o0] < nrm[o1]) { const int t = o0; o0 = o1; o1 = t; }
-  if (nrm[o0] < nrm[o2]) { const int t = o0; o0 = o2; o2 = t; }
-  if (nrm[o1] < nrm[o2]) { const int t = o1; o1 = o2; o2 = t; }
-  const int ord[3] = {o0, o1, o2};
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    S[c] = sqrt(nrm[ord[c]]);
+  for (int c = 0; c < 3; ++c)
 #pragma unroll
     for (int r = 0; r < 3; ++r) V[r * 3 + c] = W[r * 3 + ord[c]];
-  }
-  // U columns: normalised G columns; re-orthogonalised (Gram-Schmidt) so that tiny singular values do not leak noise
-  double u0[3], u1[3], u2[3];
-#pragma unroll
-  for (int r = 0; r < 3; ++r) u0[r] = S[0] > 1e-300 ? G[r * 3 + o0] / S[0] : (r == 0 ? 1.0 : 0.0);
-  double d01 = 0.0;
-#pragma unroll
-  for (int r = 0; r < 3; ++r) { u1[r] = G[r * 3 + o1]; d01 += u0[r] * u1[r]; }
-#pragma unroll
-  for (int r = 0; r < 3; ++r) u1[r] -= d01 * u0[r];
-  double n1 = sqrt(u1[0] * u1[0] + u1[1] * u1[1] + u1[2] * u1[2]);
-  if (!(n1 > 1e-12 * S[0]) || !(n1 > 1e-300)) {   // rank 1: any perpendicular
-    const int ax = fabs(u0[0]) <= fabs(u0[1]) && fabs(u0[0]) <= fabs(u0[2]) ? 0 : (fabs(u0[1]) <= fabs(u0[2]) ? 1 : 2);
-    double e[3] = {0, 0, 0};
-    e[ax] = 1.0;
-#pragma unroll
-    for (int r = 0; r < 3; ++r) u1[r] = e[r] - u0[ax] * u0[r];
-    n1 = sqrt(u1[0] * u1[0] + u1[1] * u1[1] + u1[2] * u1[2]);
-  }
-#pragma unroll
-  for (int r = 0; r < 3; ++r) u1[r] /= n1;
-  u2[0] = u0[1] * u1[2] - u0[2] * u1[1];
-  u2[1] = u0[2] * u1[0] - u0[0] * u1[2];
-  u2[2] = u0[0] * u1[1] - u0[1] * u1[0];
-  const double dir = u2[0] * G[o2] + u2[1] * G[3 + o2] + u2[2] * G[6 + o2];   // the third column itself, when it is not noise
+  cross3(u0, u1, u2);
+  const double dir = u2[0] * G[ord[2]] + u2[1] * G[3 + ord[2]] + u2[2] * G[6 + ord[2]];   // the third column itself, when it is not noise
   if (dir < 0.0 && S[2] > 1e-12 * S[0]) {
 #pragma unroll
     for (int r = 0; r < 3; ++r) u2[r] = -u2[r];
@@ -267,52 +207,34 @@ __global__ __launch_bounds__(256) void tail_fwd_kernel(TailParams p, float* __re
   float* sX = lds;
   float* sY = lds + (size_t)p.S * 3;
   const int r = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  for (int i = threadIdx.x; i < p.S * 3; i += 256) {
-    sX[i] = p.X[(long long)r * p.S * 3 + i];
-    sY[i] = p.Y[(long long)r * p.S * 3 + i];
-  }
+  stage_set(p.X, p.Y, r, p.S, sX, sY);
   __syncthreads();
   const int b = r / p.it_matches;
   for (int h = wave; h < p.itr; h += 4) {
     const long long hyp = (long long)r * p.itr + h;
     const float* w = p.mask + hyp * p.S;
-    double sw = 0.0, sa[3] = {0, 0, 0}, sb[3] = {0, 0, 0};
     float wl[TT_SLOTS];
 #pragma unroll
     for (int q = 0; q < TT_SLOTS; ++q) {
       const int j = q * 64 + lane;
       wl[q] = j < p.S ? w[j] : 0.f;
-      if (wl[q] != 0.f) {
-        sw += fabs((double)wl[q]);
-#pragma unroll
-        for (int a = 0; a < 3; ++a) { sa[a] += (double)wl[q] * sX[j * 3 + a]; sb[a] += (double)wl[q] * sY[j * 3 + a]; }
-      }
     }
-    sw = wave_sum_d(sw);
-    const double inv = 1.0 / (sw + 1e-16);
-    double am[3], bm[3];
+    double sw, am[3], bm[3], H[9], U[9], Sg[3], V[9], Vz[9];
+    procrustes_moments<double>(
+        sX, sY,
+        [=](auto&& f) {   // (captures by value: by reference the compiler keeps more SGPRs live across this file's kernels)
 #pragma unroll
-    for (int a = 0; a < 3; ++a) { am[a] = wave_sum_d(sa[a]) * inv; bm[a] = wave_sum_d(sb[a]) * inv; }
-    double hl[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-#pragma unroll
-    for (int q = 0; q < TT_SLOTS; ++q)
-      if (wl[q] != 0.f) {
-        const int j = q * 64 + lane;
-#pragma unroll
-        for (int a = 0; a < 3; ++a)
-#pragma unroll
-          for (int c = 0; c < 3; ++c) hl[a * 3 + c] += (double)wl[q] * ((double)sX[j * 3 + a] - am[a]) * ((double)sY[j * 3 + c] - bm[c]);
-      }
-    double H[9], U[9], Sg[3], V[9];
-#pragma unroll
-    for (int i = 0; i < 9; ++i) H[i] = wave_sum_d(hl[i]);
+          for (int q = 0; q < TT_SLOTS; ++q)
+            if (wl[q] != 0.f) f(q * 64 + lane, (double)wl[q]);
+        },
+        [](double v) { return wave_sum_d(v); }, [](double) { return true; }, sw, am, bm, H);
     svd3(H, U, Sg, V);
     const double d = det3(U) * det3(V) >= 0.0 ? 1.0 : -1.0;   // sign det(U V^T)
+    // R = V diag(1, 1, d) U^T
+#pragma unroll
+    for (int i = 0; i < 9; ++i) Vz[i] = i % 3 == 2 ? d * V[i] : V[i];
     float R[9], t[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a)
-#pragma unroll
-      for (int c = 0; c < 3; ++c) R[a * 3 + c] = (float)(V[a * 3] * U[c * 3] + V[a * 3 + 1] * U[c * 3 + 1] + d * V[a * 3 + 2] * U[c * 3 + 2]);
+    mul3<false, true>(Vz, U, R);
 #pragma unroll
     for (int a = 0; a < 3; ++a) t[a] = (float)bm[a] - (R[a * 3] * (float)am[0] + R[a * 3 + 1] * (float)am[1] + R[a * 3 + 2] * (float)am[2]);
     // soft inlier score over ALL matches of the set (training_utils.py:55-61)
@@ -358,10 +280,7 @@ __global__ __launch_bounds__(256) void tail_bwd_hyp_kernel(TailParams p, const f
   float* sX = lds;
   float* sY = lds + (size_t)p.S * 3;
   const int r = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  for (int i = threadIdx.x; i < p.S * 3; i += 256) {
-    sX[i] = p.X[(long long)r * p.S * 3 + i];
-    sY[i] = p.Y[(long long)r * p.S * 3 + i];
-  }
+  stage_set(p.X, p.Y, r, p.S, sX, sY);
   __syncthreads();
   const int b = r / p.it_matches;
   for (int h = wave; h < p.itr; h += 4) {

@@ -563,3 +563,69 @@ def test_inner_three_sample_is_sequential_sampling_without_replacement():
     _, _, _, d3 = ops.ransac_hypotheses(X[:1].contiguous(), Y[:1].contiguous(), w2, 8, 0.3, seed=1, offset=0)
     d3 = d3.long().cpu()
     assert bool((d3[:, 0] == 17).all()) and bool((d3[:, 1] == 0).all()) and bool((d3[:, 2] == 1).all())
+
+
+def _kabsch64(x, y, w=None):
+    """fp64 weighted Procrustes of the reference (solvers.py): R = V diag(1, 1, d) U^T for H = U S V^T, t = bbar - R abar"""
+    x, y = x.double(), y.double()
+    w = torch.ones(x.shape[0], dtype=torch.float64) if w is None else w.double()
+    inv = 1.0 / (w.abs().sum() + 1e-16)
+    am, bm = (w[:, None] * x).sum(0) * inv, (w[:, None] * y).sum(0) * inv
+    H = (w[:, None] * (x - am)).T @ (y - bm)
+    U, S, Vh = torch.linalg.svd(H)
+    d = 1.0 if float(torch.linalg.det(Vh.T @ U.T)) >= 0.0 else -1.0
+    R = Vh.T @ torch.diag(torch.tensor([1.0, 1.0, d], dtype=torch.float64)) @ U.T
+    return R, bm - R @ am, S, d
+
+
+def test_kabsch_degenerate_and_mirrored_sets():
+    """The rigid fit of both solver halves on the inputs that take its rare branches.  (a) mk_ransac_hypotheses on a generic, a
+    collinear, a two-coincident and a three-coincident triple: every R finite and a rotation, the generic one within 1e-4 of an
+    fp64 Kabsch.  (b) mk_train_tail_fwd on a proper and a mirrored set, all matches and every third: R | t within 1e-4 of the
+    fp64 formula, the saved d = +1 / -1; H's singular values are well separated, so the comparison is well conditioned."""
+    from mickey_amd import ops
+    dev = _dev()
+    gen = torch.Generator().manual_seed(7)
+    scale = torch.tensor([3.0, 2.0, 1.0], dtype=torch.float64)
+    Xs = torch.randn((65, 3), generator=gen, dtype=torch.float64) * scale
+    Q, r = torch.linalg.qr(torch.randn((3, 3), generator=gen, dtype=torch.float64))
+    Q = Q * torch.linalg.det(Q)                                  # a proper rotation
+    t0 = torch.randn((3,), generator=gen, dtype=torch.float64)
+    # (a) k = 8: rows 0, 1, 2 collinear, rows 3 = 4, rows 5 = 6 = 7
+    X = Xs[:8].clone()
+    X[2] = 2.0 * X[1] - X[0]
+    X[4] = X[3]
+    X[6] = X[7] = X[5]
+    X = X.float()
+    Y = (X.double() @ Q.T + t0).float()
+    triples = torch.tensor([[0, 3, 5], [0, 1, 2], [3, 4, 0], [5, 6, 7]])
+    Rh, th, _, idx3 = ops.ransac_hypotheses(X[None].to(dev), Y[None].to(dev), torch.ones((1, 8), device=dev), 4, 0.3,
+                                            idx3_in=triples.int().to(dev))
+    assert torch.equal(idx3.cpu().long(), triples)
+    assert bool(torch.isfinite(Rh).all()) and bool(torch.isfinite(th).all())
+    det = torch.linalg.det(Rh.cpu().reshape(-1, 3, 3).double())
+    print("det R - 1:", (det - 1).tolist())
+    assert float((det - 1).abs().max()) < 1e-5
+    Rref, tref, S, _ = _kabsch64(X[triples[0]], Y[triples[0]])
+    assert float(S[0] / S[1]) < 1e3                              # the generic triple is far from collinear
+    dR, dt = float((Rh[0].cpu().reshape(3, 3).double() - Rref).norm()), float((th[0].cpu().double() - tref).norm())
+    print("generic triple: |dR| %.3g |dt| %.3g, s1 / s2 = %.3g" % (dR, dt, float(S[0] / S[1])))
+    assert dR < 1e-4 and dt < 1e-4
+    # (b) S = 65, 5 hypotheses per set, POSE_ERR (no intrinsics); set 0 proper, set 1 mirrored; masks alternate full / every third
+    X = Xs.float()
+    M = torch.diag(torch.tensor([1.0, 1.0, -1.0], dtype=torch.float64))
+    Y = torch.stack([(X.double() @ Q.T + t0).float(), (X.double() @ (Q @ M).T + t0).float()])
+    full, third = torch.ones(65), (torch.arange(65) % 3 == 0).float()
+    mask = torch.stack([full, third, full, third, full] * 2)
+    out, Rt, saved = ops.train_tail_fwd(X[None].repeat(2, 1, 1).to(dev), Y.to(dev), mask.to(dev), Q.float()[None].repeat(2, 1, 1).to(dev),
+                                        t0.float()[None].repeat(2, 1).to(dev), None, None, 5, 1, 0.15, 1, 0)
+    Rt, saved = Rt.cpu().double(), saved.cpu()
+    for s in range(2):
+        for h in range(5):
+            Rref, tref, S, d = _kabsch64(X, Y[s], mask[s * 5 + h])
+            assert float(S[0] / S[1]) >= 1.5 and float(S[1] / S[2]) >= 1.5, S
+            err = float((Rt[s * 5 + h] - torch.cat([Rref.reshape(9), tref])).norm())
+            print("set %d hypothesis %d: |d(R|t)| %.3g, singular value ratios %.3g %.3g, d %+d" % (
+                s, h, err, float(S[0] / S[1]), float(S[1] / S[2]), int(saved[s * 5 + h, 21])))
+            assert err < 1e-4
+            assert d == (1.0 if s == 0 else -1.0) and float(saved[s * 5 + h, 21]) == d
