@@ -180,7 +180,9 @@ int mk_layernorm_planes(const float* x, int ldx, const float* w, const float* b,
 
 /* Non-causal multi-head attention, softmax(q k^T) v with head_dim 64 (layers/attention.py:53-59),
  * flash style (the ntok x ntok matrix is never materialised).  q/k/vt as written by mk_gemm_qkv;
- * out lp [nimg*ntok, ldo] with column head*64 + d. */
+ * out lp [nimg*ntok, ldo] with column head*64 + d.  No output bit depends on what the pad rows (token >= ntok) of q and k hold:
+ * pad queries take no part in any wave-wide decision and masked scores are overwritten before use; the pad columns of vt MUST be zero (a masked key
+ * has P = 0 exactly and is still multiplied into them). */
 int mk_flash_attn_fwd(const void* q, const void* k, const void* vt, void* out, int ldo, int nimg, int heads, int ntok,
                       int ntok_pad, int dtype, mk_stream_t stream);
 

@@ -335,8 +335,11 @@ __device__ __forceinline__ void attn_fold_wave(const T* __restrict__ Qh, const T
       bool rebase = first;
       if (!first) {
         rs = exp_sum();
-        rebase = __any(!(rs <= ATT_REBASE_SUM));   // also true for +inf (an overflowed sum); the file is built with
-                                                   // -fno-honor-nans, so nothing is claimed for NaN: finite q, k cannot make one
+        // also true for +inf (an overflowed sum); the file is built with -fno-honor-nans, so nothing is claimed for NaN: finite
+        // q, k cannot make one.  Pad queries (row >= ntok: never stored) have no vote: the decision is wave-uniform, and with one
+        // what a pad row of q holds would decide whether its live neighbours re-base -- same value, other last bits.  On a
+        // zero-filled pad row (the caller's contract, mickey_hip.h) a lane's sum is at most 32, which never voted: no bit changes.
+        rebase = __any(!(rs <= ATT_REBASE_SUM) && q0 + qb * 32 + j < ntok);
       }
       if (rebase) {   // the first tile, and tiles that outgrew m: re-base m to this tile's maximum
         float t8[8];
@@ -544,7 +547,7 @@ __global__ __launch_bounds__(256, QB == 2 ? 2 : 3) void attn_fwd_fold16_kernel(c
         bool rebase = first;
         if (!first) {
           rs = exp_sum();
-          rebase = __any(!(rs <= ATT_REBASE_SUM));
+          rebase = __any(!(rs <= ATT_REBASE_SUM) && q0 + qb * 32 + nb * 16 + n < ntok);   // pad queries have no vote (see attn_fold_wave)
         }
         if (rebase) {
           float t4[4];
