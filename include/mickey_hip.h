@@ -418,6 +418,44 @@ int mk_train_ln128_fwd(const float* u, const float* gamma, const float* beta, fl
 int mk_train_ln128_bwd(const float* g, const float* xhat, const float* rstd, const float* gamma, float* gu, float* part,
                        long long part_stride, int M, mk_stream_t stream);
 
+/* The head tails for TRAINING (mickey_extractor.py:98-124 remove_borders / remove_brd_and_softmax, 134-140 the detector's score conv,
+ * 172-176 xy_offset + sigmoid, 211-216 depth (+ max_depth sigmoid), 248-249 with utils/extractor_utils.py:6-10 desc_l2norm, all
+ * under autograd; mk_head_tails below is their inference form).  fp32, vector ALU only; every sum in an order fixed by the shape
+ * (no atomics, no host sync): bit-identical from run to run, an image's forward and input-gradient rows do not depend on the other
+ * images, gradients are bit-linear in the incoming gradient under a power-of-two scale.  feat / gfeat / x / gx are dense rows
+ * [nimg n, C] (channels_last memory), n = h wd pixels per image, C a multiple of 4 in [4, 256], 16-byte aligned.
+ *
+ * mk_train_headtail_fwd: z[o, p] = sum_c feat[p, c] w[o, c], o < Cout in {1, 2}, w [Cout, C] dense; out [nimg, Cout, n] =
+ *   MK_TAIL_IDENTITY        z                                                              (depth)
+ *   MK_TAIL_SIGMOID         scale sigmoid(z)                    (offset: scale 1; depth with use_depth_sigmoid: scale max_depth)
+ *   MK_TAIL_MASKED_SIGMOID  in_p sigmoid(z),  in_p = 1 on pixels at least `border` from every edge, else 0       (Cout == 1)
+ *   MK_TAIL_SOFTMAX         per image: mean = sum_p z_p / n + eps over ALL pixels (a constant of the backward: the reference detaches
+ *                           it), e_p = in_p exp((z_p - mean) / temperature), y_p = e_p / (sum_p e_p + eps)       (Cout == 1;
+ *                           a second launch, one workgroup per image)
+ * mk_train_headtail_bwd: g, y [nimg, Cout, n] (y = the forward's output; unused for MK_TAIL_IDENTITY).
+ *   gz = g (identity),  g y (1 - y / scale) (both sigmoids; the masked one with scale 1: y == 0 outside the border),
+ *   gz_p = (y_p / temperature) (g_p - dot_img) with dot_img = sum_q g_q y_q over the image's pixels (softmax: exact including eps,
+ *   dy_i/dz_k = (delta_ik y_i - y_i y_k) / temperature; dot [nimg] is work memory, written by a launch of its own).
+ *   gfeat[p, c] = sum_o gz[o, p] w[o, c]  (gfeat NULL: not wanted, no pass over it);
+ *   gw[o, c] = sum_p gz[o, p] feat[p, c]  (gw NULL: not wanted, feat is not read): chunk k of mk_train_headtail_chunk_rows() rows
+ *   leaves its sum in part[k Cout C ..], mk_train_headtail_chunks(rows) chunks (a function of the row count alone), which a last
+ *   launch adds in chunk order (sixteen consecutive runs of chunks, then the sixteen sums in order).  At most 3 launches; none
+ *   when neither output is wanted.
+ * mk_train_desc_l2norm_fwd: y[img, c, p] = x[p, c] rnorm_p, rnorm_p = 1 / sqrt(sum_c x[p, c]^2 + eps); y [nimg, C, n] (transposed,
+ *   the layout the matcher reads), rnorm [nimg n] (NULL: not kept).  The bits of mk_head_tails' dsc.
+ * mk_train_desc_l2norm_bwd: gx[p, c] = rnorm_p (g[img, c, p] - y[img, c, p] sum_c g[img, c, p] y[img, c, p]), g and y [nimg, C, n]. */
+enum { MK_TAIL_IDENTITY = 0, MK_TAIL_SIGMOID = 1, MK_TAIL_MASKED_SIGMOID = 2, MK_TAIL_SOFTMAX = 3 };
+int mk_train_headtail_chunk_rows(void);
+int mk_train_headtail_chunks(long long rows);
+int mk_train_headtail_fwd(const float* feat, const float* w, float* out, int nimg, int h, int wd, int C, int Cout, int act,
+                          float scale, int border, float temperature, float eps, mk_stream_t stream);
+int mk_train_headtail_bwd(const float* g, const float* y, const float* feat, const float* w, float* dot, float* gfeat, float* part,
+                          float* gw, int nimg, int n, int C, int Cout, int act, float scale, float temperature,
+                          mk_stream_t stream);
+int mk_train_desc_l2norm_fwd(const float* x, float* y, float* rnorm, int nimg, int n, int C, float eps, mk_stream_t stream);
+int mk_train_desc_l2norm_bwd(const float* g, const float* y, const float* rnorm, float* gx, int nimg, int n, int C,
+                             mk_stream_t stream);
+
 /* Head tails (mickey_extractor.py:134-138,173-176,213-216,246-249 and
  * compute_correspondences.py:20-31).  feat* fp32 [nimg*h*w, C] (resblock4 outputs).
  *   scr   [nimg, h*w]      border-masked temperature-100 softmax (or sigmoid) of w_score . feat_det

@@ -72,6 +72,12 @@ SIGNATURES = {
     "mk_train_tail": ("i", "plilplilpp"),
     "mk_train_ln128_fwd": ("i", "pppfplpppip"),
     "mk_train_ln128_bwd": ("i", "pppppplip"),
+    "mk_train_headtail_chunk_rows": ("i", ""),
+    "mk_train_headtail_chunks": ("i", "l"),
+    "mk_train_headtail_fwd": ("i", "pppiiiiiififfp"),
+    "mk_train_headtail_bwd": ("i", "ppppppppiiiiiffp"),
+    "mk_train_desc_l2norm_fwd": ("i", "pppiiifp"),
+    "mk_train_desc_l2norm_bwd": ("i", "ppppiiip"),
     "mk_head_tails": ("i", "pppppppppppiiiiiiiififp"),
     "mk_dual_softmax_work_floats": ("l", "iiii"),
     "mk_dual_softmax": ("i", "ppppfifppppiiiip"),

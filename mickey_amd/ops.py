@@ -580,6 +580,86 @@ def train_ln128_bwd(g, xhat, rstd, gamma, gu=None, part=None, part_stride=256):
     call("mk_train_ln128_bwd", ptr(g), ptr(xhat), ptr(rstd), ptr(gamma), ptr(gu), ptr(part), part_stride, M, stream())
 
 
+# ---- training: the head tails (mickey_hip.h: mk_train_headtail_* / mk_train_desc_l2norm_*; train_tails.py).  Features are 2-D fp32
+# [nimg h w, C] tensors with dense, 16-byte aligned rows; outputs may be passed in (tests place them in guarded windows). ----------
+TAIL_IDENTITY, TAIL_SIGMOID, TAIL_MASKED_SIGMOID, TAIL_SOFTMAX = 0, 1, 2, 3
+HEADTAIL_CHUNK_ROWS = 208   # rows of one weight-gradient partial == mk_train_headtail_chunk_rows() (tests/test_train_tails_cpu.py)
+TAIL_MIN_C, TAIL_MAX_C = 4, 256
+
+
+def headtail_chunks(rows):
+    """chunks of the weight gradient of a `rows`-row 1x1 tail: a function of the row count alone."""
+    return -(-rows // HEADTAIL_CHUNK_ROWS) if rows > 0 else 0   # == mk_train_headtail_chunks(rows), without the call
+
+
+def _dense(t):
+    assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.data_ptr() % 16 == 0
+    return t
+
+
+def train_headtail_fwd(feat, w, nimg, h, wd, act, scale=1.0, border=0, temperature=1.0, eps=0.0, out=None):
+    """mk_train_headtail_fwd: feat [nimg h wd, C], w [Cout, C] -> out [nimg, Cout, h wd] (1 launch; 2 for TAIL_SOFTMAX)."""
+    C, Cout = feat.shape[1], w.shape[0]
+    assert feat.shape[0] == nimg * h * wd and w.shape[1] == C
+    if out is None:
+        out = torch.empty((nimg, Cout, h * wd), device=feat.device, dtype=torch.float32)
+    assert out.is_contiguous() and out.numel() == nimg * Cout * h * wd
+    call("mk_train_headtail_fwd", ptr(_dense(feat)), ptr(_dense(w)), ptr(out), nimg, h, wd, C, Cout, int(act), float(scale), int(border),
+         float(temperature), float(eps), stream())
+    return out
+
+
+def train_headtail_bwd(g, y, feat, w, nimg, n, act, scale=1.0, temperature=1.0, want_gfeat=True, want_gw=True, gfeat=None, gw=None,
+                       part=None):
+    """mk_train_headtail_bwd: g, y [nimg, Cout, n] -> (gfeat [nimg n, C] or None, gw [Cout, C] or None); at most 3 launches, none of
+    the weight-gradient work without want_gw, no pass over gfeat without want_gfeat."""
+    Cout, C = w.shape
+    dev = g.device
+    assert g.is_contiguous() and g.dtype == torch.float32 and g.numel() == nimg * Cout * n and (y is None or y.is_contiguous())
+    chunks = headtail_chunks(nimg * n) if want_gw else 0
+    nw = Cout * C
+    # one allocation for the work memory of a call: chunk partials | gw | the per-image dots of the softmax
+    need = ((chunks * nw if part is None else 0) + (nw if gw is None else 0) if want_gw else 0) + (nimg if act == TAIL_SOFTMAX else 0)
+    work = torch.empty((need,), device=dev, dtype=torch.float32) if need else None
+    off = 0
+    if want_gw:
+        if part is None:
+            part, off = work[:chunks * nw], chunks * nw
+        if gw is None:
+            gw, off = work[off:off + nw].view(Cout, C), off + nw
+        assert part.is_contiguous() and part.numel() >= chunks * nw and part.data_ptr() % 16 == 0 and gw.is_contiguous() and gw.numel() == nw
+        _dense(feat)
+    dot = work[off:] if act == TAIL_SOFTMAX else None
+    if want_gfeat and gfeat is None:
+        gfeat = torch.empty((nimg * n, C), device=dev, dtype=torch.float32)
+    call("mk_train_headtail_bwd", ptr(g), ptr(y), ptr(feat) if want_gw else None, ptr(_dense(w)), ptr(dot),
+         ptr(_dense(gfeat)) if want_gfeat else None, ptr(part) if want_gw else None, ptr(gw) if want_gw else None, nimg, n, C, Cout,
+         int(act), float(scale), float(temperature), stream())
+    return (gfeat if want_gfeat else None), (gw if want_gw else None)
+
+
+def train_desc_l2norm_fwd(x, nimg, n, eps, want_saved=True, out=None):
+    """mk_train_desc_l2norm_fwd: x [nimg n, C] -> (y [nimg, C, n], rnorm [nimg n] or None)."""
+    C = x.shape[1]
+    assert x.shape[0] == nimg * n
+    if out is None:
+        out = torch.empty((nimg, C, n), device=x.device, dtype=torch.float32)
+    assert out.is_contiguous() and out.numel() == nimg * C * n
+    rnorm = torch.empty((nimg * n,), device=x.device, dtype=torch.float32) if want_saved else None
+    call("mk_train_desc_l2norm_fwd", ptr(_dense(x)), ptr(out), ptr(rnorm), nimg, n, C, float(eps), stream())
+    return out, rnorm
+
+
+def train_desc_l2norm_bwd(g, y, rnorm, nimg, n, C, out=None):
+    """mk_train_desc_l2norm_bwd: g, y [nimg, C, n], rnorm [nimg n] -> gx [nimg n, C]."""
+    assert g.is_contiguous() and y.is_contiguous() and g.dtype == torch.float32 and g.numel() == y.numel() == nimg * C * n
+    if out is None:
+        out = torch.empty((nimg * n, C), device=g.device, dtype=torch.float32)
+    assert out.is_contiguous() and out.numel() == nimg * n * C
+    call("mk_train_desc_l2norm_bwd", ptr(g), ptr(y), ptr(rnorm), ptr(out), nimg, n, C, stream())
+    return out
+
+
 def head_tails(f_det, w_score, f_off, w_xy, f_dep, w_dep, f_dsc, nimg, h, w, C, Cd, border=3, use_softmax=True,
                use_depth_sigmoid=False, max_depth=60.0, norm_dsc=True, down=14.0):
     dev = f_det.device
