@@ -27,14 +27,12 @@ Not covered here: the q / k / v / merge / MLP nn.Linears and the LayerNorms of E
 around this core as one node); BatchNorm, ReLU and the 1x1 convolutions (they stay in torch); autocast and half-precision inputs (ValueError); double backward; head sizes other than 16; hipGraph capture
 of a step.
 """
-import math
-import numbers
-
 import torch
 from torch import nn
 from torch.autograd.function import once_differentiable
 
-from . import _native, ops
+from . import ops
+from ._train_common import aligned_copy, check_devices, check_f32, check_grad, check_number, is_number, rows_in_place, swap_modules
 
 HEAD_DIM = 16
 MAX_CHANNELS = 128
@@ -81,44 +79,28 @@ def linear_attention_grads(q, k, v, go, eps=1e-6):
 # ---- the op ----------------------------------------------------------------------------------------------------------------
 def _validate(q, k, v, eps):
     """Every check of linear_attention_train, on the host, before anything is launched."""
+    fn = "linear_attention_train"
     for name, t in (("q", q), ("k", k), ("v", v)):
-        if not torch.is_tensor(t):
-            raise ValueError("linear_attention_train: %s must be a tensor, got %s" % (name, type(t).__name__))
-        if t.dtype != torch.float32:
-            raise ValueError("linear_attention_train: %s must be float32, got %s (autocast is not covered)" % (name, t.dtype))
-        if t.dim() != 4:
-            raise ValueError("linear_attention_train: %s must be [N, tokens, H, %d], got %s" % (name, HEAD_DIM, tuple(t.shape)))
-        if t.shape[3] != HEAD_DIM:
-            raise ValueError("linear_attention_train: heads of %d channels only, %s is %s" % (HEAD_DIM, name, tuple(t.shape)))
-        if min(t.shape) < 1:
-            raise ValueError("linear_attention_train: empty %s %s" % (name, tuple(t.shape)))
+        check_f32(fn, name, t, rank=4, width=HEAD_DIM, why=" ([N, tokens, H, 16]: heads of 16 channels only)")
     if q.shape[2] * HEAD_DIM > MAX_CHANNELS:
-        raise ValueError("linear_attention_train: at most %d channels (%d heads), got %d heads"
-                         % (MAX_CHANNELS, MAX_CHANNELS // HEAD_DIM, q.shape[2]))
+        raise ValueError("%s: at most %d channels (%d heads), got %d heads" % (fn, MAX_CHANNELS, MAX_CHANNELS // HEAD_DIM, q.shape[2]))
     if k.shape[0] != q.shape[0] or k.shape[2] != q.shape[2]:
-        raise ValueError("linear_attention_train: q %s and k %s must share N and H" % (tuple(q.shape), tuple(k.shape)))
+        raise ValueError("%s: q %s and k %s must share N and H" % (fn, tuple(q.shape), tuple(k.shape)))
     if tuple(v.shape) != tuple(k.shape):
-        raise ValueError("linear_attention_train: k %s and v %s must have the same shape" % (tuple(k.shape), tuple(v.shape)))
-    if isinstance(eps, bool) or not isinstance(eps, numbers.Real) or not math.isfinite(float(eps)) or float(eps) < 0:
-        raise ValueError("linear_attention_train: eps must be a finite non-negative number, got %r" % (eps,))
-    if not (q.is_cuda and k.is_cuda and v.is_cuda):
-        raise _native.MickeyHipError("linear_attention_train needs device tensors (q on %s, k on %s, v on %s); mickey_amd has no "
-                                     "CPU fallback" % (q.device, k.device, v.device))
-    if k.device != q.device or v.device != q.device:
-        raise ValueError("linear_attention_train: q on %s, k on %s, v on %s" % (q.device, k.device, v.device))
+        raise ValueError("%s: k %s and v %s must have the same shape" % (fn, tuple(k.shape), tuple(v.shape)))
+    check_number(fn, "eps", eps)
+    check_devices(fn, [("q", q), ("k", k), ("v", v)])
 
 
 def _rows(t):
-    """The tensor itself when the kernels can read it in place (the last two dimensions dense, 16-byte aligned rows that do not
-    overlap), else a contiguous, aligned copy."""
+    """The [N, T, H, 16] tensor itself when the kernels can read it in place (the last two dimensions dense, token rows by
+    _train_common.rows_in_place, images any non-negative multiple of 4 elements apart), else a contiguous, aligned copy."""
     N, T, H, _ = t.shape
     C = H * HEAD_DIM
-    ok = (t.stride(3) == 1 and (H == 1 or t.stride(2) == HEAD_DIM) and (T == 1 or (t.stride(1) >= C and t.stride(1) % 4 == 0))
-          and (N == 1 or (t.stride(0) >= 0 and t.stride(0) % 4 == 0)) and t.data_ptr() % 16 == 0)
-    if ok:
+    if ((H == 1 or t.stride(2) == HEAD_DIM) and (N == 1 or (t.stride(0) >= 0 and t.stride(0) % 4 == 0))
+            and rows_in_place(t, C, t.stride(1) if T > 1 else C)):
         return t
-    c = t.contiguous()
-    return c if c.data_ptr() % 16 == 0 else c.clone()   # (a dense tensor at an odd offset of its storage)
+    return aligned_copy(t)
 
 
 class LinearAttentionTrainFn(torch.autograd.Function):
@@ -138,8 +120,7 @@ class LinearAttentionTrainFn(torch.autograd.Function):
     @once_differentiable
     def backward(ctx, go):
         q, k, v, kv = ctx.saved_tensors
-        if go.dtype != torch.float32:
-            raise ValueError("linear_attention_train backward: the incoming gradient must be float32, got %s" % go.dtype)
+        check_grad("linear_attention_train", go)
         with torch.cuda.device(go.device):
             gq, gk, gv = ops.linattn_train_bwd(q, k, v, kv, go.contiguous(), ctx.eps, tuple(ctx.needs_input_grad[:3]))
         return gq, gk, gv, None
@@ -163,8 +144,7 @@ class LinearAttention(nn.Module):
 
     def __init__(self, eps=1e-6):
         super().__init__()
-        if isinstance(eps, bool) or not isinstance(eps, numbers.Real) or not math.isfinite(float(eps)) or float(eps) < 0:
-            raise ValueError("LinearAttention: eps must be a finite non-negative number, got %r" % (eps,))
+        check_number("LinearAttention", "eps", eps)
         self.eps = eps
         self.attention = "linear"
 
@@ -185,8 +165,7 @@ def _is_linear_attention(m):
         return False
     if getattr(m, "attention", None) != "linear":
         return False
-    eps = getattr(m, "eps", None)
-    if isinstance(eps, bool) or not isinstance(eps, numbers.Real) or not math.isfinite(float(eps)) or float(eps) < 0:
+    if not is_number(getattr(m, "eps", None)):
         return False
     if next(m.parameters(), None) is not None:
         return False
@@ -207,14 +186,8 @@ def use_hip_attention(model):
     numeric eps, no parameters, feature_map == elu + 1) by a LinearAttention with the same eps.  'full' and 'flash' attention
     modules and everything else are left alone; the modules swapped hold no parameters or buffers, so state-dict keys and
     Parameter objects do not change.  Returns the number of modules swapped; a second call finds none."""
-    swapped = 0
-    made = {}   # a module registered under several parents stays ONE module
-    for parent in list(model.modules()):
-        for name, child in list(parent._modules.items()):
-            if child is not None and _is_linear_attention(child):
-                if id(child) not in made:
-                    made[id(child)] = LinearAttention(child.eps)
-                    made[id(child)].train(child.training)
-                parent._modules[name] = made[id(child)]
-                swapped += 1
-    return swapped
+    def make(m):
+        if _is_linear_attention(m):
+            return LinearAttention(m.eps).train(m.training)
+
+    return swap_modules(model, make)

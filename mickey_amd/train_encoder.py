@@ -21,6 +21,7 @@ from torch import nn
 
 from . import _native, pipeline
 from . import weights as wts_mod
+from ._train_common import swap_modules
 
 _DTYPES = {"bf16": torch.bfloat16, "fp16": torch.float16, "fp32": torch.float32}
 _TOP_KEYS = ("cls_token", "pos_embed", "patch_embed.proj.weight", "patch_embed.proj.bias", "norm.weight", "norm.bias")
@@ -254,16 +255,8 @@ def use_hip_encoder(model, dtype="auto", ln_fold=True, features_lp="auto"):
     it has a forward_features method and DINOv2's state-dict key structure, whatever its class.  An architecture the kernels do
     not cover (register tokens, SwiGLU FFN, patch size != 14, D % 64 != 0) raises ValueError instead of being skipped.  Returns
     the number of children swapped; a second call finds none."""
-    swapped = 0
-    made = {}
-    for m in list(model.modules()):
-        old = m._modules.get("dinov2_vitl14")
-        if old is None or isinstance(old, FrozenDinoV2):
-            continue
-        if not callable(getattr(old, "forward_features", None)) or not _looks_like_dinov2(old):
-            continue
-        if id(old) not in made:
-            made[id(old)] = FrozenDinoV2(old, dtype=dtype, ln_fold=ln_fold, features_lp=features_lp)
-        m.dinov2_vitl14 = made[id(old)]
-        swapped += 1
-    return swapped
+    def make(old):
+        if not isinstance(old, FrozenDinoV2) and callable(getattr(old, "forward_features", None)) and _looks_like_dinov2(old):
+            return FrozenDinoV2(old, dtype=dtype, ln_fold=ln_fold, features_lp=features_lp)   # (stays in eval mode, whatever old's)
+
+    return swap_modules(model, make, name="dinov2_vitl14")

@@ -25,7 +25,8 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
-from . import _native, ops
+from . import ops
+from ._train_common import check_devices, check_f32, check_grad, check_tensor, swap_modules
 
 
 # ---- the formulas the kernels implement, as plain torch (any device, any float dtype: tests, documentation) --------------------
@@ -80,24 +81,18 @@ def supported_channels(cin, cout):
 
 def _validate(x, weight):
     """Every check of conv3x3_train, on the host, before anything is launched."""
-    if not torch.is_tensor(x) or not torch.is_tensor(weight):
-        raise ValueError("conv3x3_train: x and weight must be tensors")
-    if not x.is_cuda or not weight.is_cuda:
-        raise _native.MickeyHipError("conv3x3_train needs device tensors (x on %s, weight on %s); mickey_amd has no CPU fallback"
-                                     % (x.device, weight.device))
-    if x.device != weight.device:
-        raise ValueError("conv3x3_train: x on %s, weight on %s" % (x.device, weight.device))
-    if x.dtype != torch.float32 or weight.dtype != torch.float32:
-        raise ValueError("conv3x3_train: x and weight must be float32, got %s and %s (autocast is not covered)" % (x.dtype, weight.dtype))
-    if x.dim() != 4 or weight.dim() != 4 or tuple(weight.shape[2:]) != (3, 3):
-        raise ValueError("conv3x3_train: x must be [B, Cin, H, W] and weight [Cout, Cin, 3, 3], got %s and %s"
-                         % (tuple(x.shape), tuple(weight.shape)))
+    fn = "conv3x3_train"
+    check_tensor(fn, "x", x)
+    check_tensor(fn, "weight", weight)
+    check_devices(fn, [("x", x), ("weight", weight)])   # (this op looks at the devices before the dtypes: a CPU half tensor is a MickeyHipError)
+    check_f32(fn, "x", x, rank=4, why=" ([B, Cin, H, W])")
+    check_f32(fn, "weight", weight, rank=4, why=" ([Cout, Cin, 3, 3])")
+    if tuple(weight.shape[2:]) != (3, 3):
+        raise ValueError("%s: weight must be [Cout, Cin, 3, 3], got %s" % (fn, tuple(weight.shape)))
     if x.shape[1] != weight.shape[1]:
-        raise ValueError("conv3x3_train: x has %d channels, weight expects %d" % (x.shape[1], weight.shape[1]))
-    if min(x.shape) < 1:
-        raise ValueError("conv3x3_train: empty input %s" % (tuple(x.shape),))
+        raise ValueError("%s: x has %d channels, weight expects %d" % (fn, x.shape[1], weight.shape[1]))
     if not supported_channels(weight.shape[1], weight.shape[0]):
-        raise ValueError("conv3x3_train: Cin must be a multiple of 32 and Cout of 4, got Cin=%d, Cout=%d" % (weight.shape[1], weight.shape[0]))
+        raise ValueError("%s: Cin must be a multiple of 32 and Cout of 4, got Cin=%d, Cout=%d" % (fn, weight.shape[1], weight.shape[0]))
 
 
 def _nchw_view(rows, B, H, W, C):
@@ -131,8 +126,7 @@ class Conv3x3TrainFn(torch.autograd.Function):
     def backward(ctx, gy):
         B, Cin, Cout, H, W = ctx.geom
         buf, sx, weight, sw = ctx.saved_tensors
-        if gy.dtype != torch.float32:
-            raise ValueError("conv3x3_train backward: the incoming gradient must be float32, got %s" % gy.dtype)
+        check_grad("conv3x3_train", gy)
         Cp = (Cout + 31) // 32 * 32
         gx = dw = None
         with torch.cuda.device(gy.device):
@@ -199,14 +193,8 @@ def use_hip_convs(model):
     padding, fp32 weights, Cin % 32 == 0 and Cout % 4 == 0 by a Conv3x3 that holds the SAME Parameter object (optimiser state and
     checkpoints stay valid; state-dict keys do not change).  Every other module is left alone.  Returns the number of
     convolutions swapped; a second call finds none."""
-    swapped = 0
-    made = {}   # a conv registered under several parents stays ONE module
-    for parent in list(model.modules()):
-        for name, child in list(parent._modules.items()):
-            if child is not None and _takes(child):
-                if id(child) not in made:
-                    made[id(child)] = Conv3x3(child.in_channels, child.out_channels, weight=child.weight)
-                    made[id(child)].train(child.training)
-                parent._modules[name] = made[id(child)]
-                swapped += 1
-    return swapped
+    def make(m):
+        if _takes(m):
+            return Conv3x3(m.in_channels, m.out_channels, weight=m.weight).train(m.training)
+
+    return swap_modules(model, make)

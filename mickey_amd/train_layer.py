@@ -26,15 +26,13 @@ Not covered: d_model other than 128 or nhead other than 8 (ValueError), biases, 
 backward, hipGraph capture of a step, BatchNorm / ReLU / the 1x1 convolutions of BasicBlock, the head tails (train_tails.py), the positional
 encoding and the NCHW <-> token rearrangement around the stack.
 """
-import math
-import numbers
-
 import torch
 import torch.nn.functional as F
 from torch import nn
 from torch.autograd.function import once_differentiable
 
-from . import _native, ops
+from . import ops
+from ._train_common import adopt, aligned_copy, check_devices, check_f32, check_grad, check_number, rows_in_place, swap_modules
 from .train_attention import LinearAttention, _is_linear_attention, linear_attention_formula
 
 D_MODEL = 128
@@ -62,62 +60,33 @@ def encoder_layer_formula(x, source, wq, wk, wv, wm, w1, w2, ln1_w, ln1_b, ln2_w
 
 
 # ---- argument checks and layouts ---------------------------------------------------------------------------------------------
-def _check_eps(fn, name, eps):
-    if isinstance(eps, bool) or not isinstance(eps, numbers.Real) or not math.isfinite(float(eps)) or float(eps) < 0:
-        raise ValueError("%s: %s must be a finite non-negative number, got %r" % (fn, name, eps))
-
-
-def _check_tensor(fn, name, t, shape=None, rank=None, width=None):
-    if not torch.is_tensor(t):
-        raise ValueError("%s: %s must be a tensor, got %s" % (fn, name, type(t).__name__))
-    if t.dtype != torch.float32:
-        raise ValueError("%s: %s must be float32, got %s (autocast is not covered)" % (fn, name, t.dtype))
-    if shape is not None and tuple(t.shape) != shape:
-        raise ValueError("%s: %s must be %s, got %s (d_model == 128 and nhead == 8 only)" % (fn, name, shape, tuple(t.shape)))
-    if rank is not None and t.dim() != rank:
-        raise ValueError("%s: %s must have %d dimensions, got %s" % (fn, name, rank, tuple(t.shape)))
-    if width is not None and (t.dim() < 1 or t.shape[-1] != width):
-        raise ValueError("%s: the last dimension of %s must be %d, got %s" % (fn, name, width, tuple(t.shape)))
-    if t.numel() == 0:
-        raise ValueError("%s: empty %s %s" % (fn, name, tuple(t.shape)))
-
-
-def _check_devices(fn, named):
-    if not all(t.is_cuda for _, t in named):
-        raise _native.MickeyHipError("%s needs device tensors (%s); mickey_amd has no CPU fallback"
-                                     % (fn, ", ".join("%s on %s" % (n, t.device) for n, t in named)))
-    if any(t.device != named[0][1].device for _, t in named):
-        raise ValueError("%s: tensors on different devices (%s)" % (fn, ", ".join("%s on %s" % (n, t.device) for n, t in named)))
+_ONLY = " (d_model == 128 and nhead == 8 only)"
 
 
 def _validate(x, source, weights, attn_eps, ln1_eps, ln2_eps):
     """Every check of encoder_layer_train, on the host, before anything is launched."""
     fn = "encoder_layer_train"
-    _check_tensor(fn, "x", x, rank=3, width=D_MODEL)
-    _check_tensor(fn, "source", source, rank=3, width=D_MODEL)
+    check_f32(fn, "x", x, rank=3, width=D_MODEL, why=_ONLY)
+    check_f32(fn, "source", source, rank=3, width=D_MODEL, why=_ONLY)
     if source.shape[0] != x.shape[0]:
         raise ValueError("%s: x %s and source %s must share N" % (fn, tuple(x.shape), tuple(source.shape)))
     for (name, shape), w in zip(_W_SHAPES, weights):
-        _check_tensor(fn, name, w, shape=shape)
+        check_f32(fn, name, w, shape=shape, why=_ONLY)
     for name, eps in (("attn_eps", attn_eps), ("ln1_eps", ln1_eps), ("ln2_eps", ln2_eps)):
-        _check_eps(fn, name, eps)
-    _check_devices(fn, [("x", x), ("source", source)] + [(n, w) for (n, _), w in zip(_W_SHAPES, weights)])
+        check_number(fn, name, eps)
+    check_devices(fn, [("x", x), ("source", source)] + [(n, w) for (n, _), w in zip(_W_SHAPES, weights)])
 
 
 def _rows2d(t):
-    """[..., C] fp32 tensor -> a 2-D [rows, C] tensor the kernels read: a view when the rows are dense, evenly spaced (a multiple
-    of 4 elements, no overlap) and 16-byte aligned (the rule of train_attention._rows), else a contiguous, aligned copy."""
+    """[..., C] fp32 tensor -> a 2-D [rows, C] tensor the kernels read: a view when t is contiguous, or 3-D with evenly spaced rows
+    (stride(0) == T * stride(1), since two dimensions become one) that _train_common.rows_in_place accepts; else a view of a
+    contiguous, aligned copy."""
     C = t.shape[-1]
     rows = t.numel() // C
-    if t.is_contiguous():
-        v = t.view(rows, C)
-    else:
-        v = None
-        if t.dim() == 3 and t.stride(2) == 1 and t.stride(1) >= C and t.stride(1) % 4 == 0 and (t.shape[0] == 1 or t.stride(0) == t.shape[1] * t.stride(1)):
-            v = t.as_strided((rows, C), (t.stride(1), 1))
-        if v is None:
-            v = t.contiguous().view(rows, C)
-    return v if v.data_ptr() % 16 == 0 else v.clone(memory_format=torch.contiguous_format)   # (a dense tensor at an odd offset of its storage)
+    if (not t.is_contiguous() and t.dim() == 3 and (t.shape[0] == 1 or t.stride(0) == t.shape[1] * t.stride(1))
+            and rows_in_place(t, C, t.stride(1))):
+        return t.as_strided((rows, C), (t.stride(1), 1))
+    return aligned_copy(t).view(rows, C)
 
 
 def _heads(t2d, N, T, col):
@@ -193,8 +162,7 @@ class EncoderLayerTrainFn(torch.autograd.Function):
         N, L, S, attn_eps, self_att = ctx.dims
         x2, proj, att, kvblk, xh1, rs1, m, h, xh2, rs2, wq, wk, wv, wm, w1, w2, g1, g2 = ctx.saved_tensors[:18]
         s2, kvp = (None, None) if self_att else ctx.saved_tensors[18:]
-        if go.dtype != torch.float32:
-            raise ValueError("encoder_layer_train backward: the incoming gradient must be float32, got %s" % go.dtype)
+        check_grad("encoder_layer_train", go)
         nx, ns = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         nwq, nwk, nwv, nwm, nw1, nw2, ng1, nb1, ng2, nb2 = ctx.needs_input_grad[6:]
         want_w = nwq or nwk or nwv or nwm or nw1 or nw2
@@ -295,7 +263,7 @@ def encoder_layer_train(x, source, wq, wk, wv, wm, w1, w2, ln1_w, ln1_b, ln2_w, 
     S = source.shape[1]
     x2 = _rows2d(x)
     s2 = None if source is x else _rows2d(source)
-    weights = tuple(w if (w.is_contiguous() and w.data_ptr() % 16 == 0) else w.contiguous().clone() for w in weights)
+    weights = tuple(aligned_copy(w) for w in weights)
     out = EncoderLayerTrainFn.apply(x2, s2, N, L, S, (float(attn_eps), float(ln1_eps), float(ln2_eps)), *weights)
     return out
 
@@ -314,8 +282,7 @@ class LinearTrainFn(torch.autograd.Function):
     @once_differentiable
     def backward(ctx, go):
         x2, w = ctx.saved_tensors
-        if go.dtype != torch.float32:
-            raise ValueError("linear_train backward: the incoming gradient must be float32, got %s" % go.dtype)
+        check_grad("linear_train", go)
         M, K = x2.shape
         N = w.shape[0]
         gx = gw = None
@@ -336,14 +303,13 @@ def linear_train(x, weight):
     """y = x W^T (nn.Linear without bias) on mk_train_linear_fwd / _dgrad / _wgrad: x fp32 [..., K] device tensor, weight [N, K],
     K and N multiples of 16.  Differentiable in both."""
     fn = "linear_train"
-    _check_tensor(fn, "x", x)
-    _check_tensor(fn, "weight", weight, rank=2)
+    check_f32(fn, "x", x)
+    check_f32(fn, "weight", weight, rank=2)
     if x.dim() < 1 or x.shape[-1] != weight.shape[1] or weight.shape[0] % 16 or weight.shape[1] % 16:
         raise ValueError("%s: x %s and weight %s must share K; K and N must be multiples of 16" % (fn, tuple(x.shape), tuple(weight.shape)))
-    _check_devices(fn, [("x", x), ("weight", weight)])
-    w = weight if (weight.is_contiguous() and weight.data_ptr() % 16 == 0) else weight.contiguous().clone()
+    check_devices(fn, [("x", x), ("weight", weight)])
     x2 = _rows2d(x if x.dim() != 1 else x[None])
-    return LinearTrainFn.apply(x2, w).view(*x.shape[:-1], weight.shape[0])
+    return LinearTrainFn.apply(x2, aligned_copy(weight)).view(*x.shape[:-1], weight.shape[0])
 
 
 class LayerNormTrainFn(torch.autograd.Function):
@@ -360,8 +326,7 @@ class LayerNormTrainFn(torch.autograd.Function):
     @once_differentiable
     def backward(ctx, go):
         xh, rs, w = ctx.saved_tensors
-        if go.dtype != torch.float32:
-            raise ValueError("layernorm_train backward: the incoming gradient must be float32, got %s" % go.dtype)
+        check_grad("layernorm_train", go)
         M = xh.shape[0]
         nx, nw, nb = ctx.needs_input_grad[:3]
         with torch.cuda.device(go.device):
@@ -378,11 +343,11 @@ class LayerNormTrainFn(torch.autograd.Function):
 def layernorm_train(x, weight, bias, eps=1e-5):
     """nn.LayerNorm(128) with affine parameters on mk_train_ln128_fwd / _bwd: x fp32 [..., 128] device tensor."""
     fn = "layernorm_train"
-    _check_tensor(fn, "x", x, width=D_MODEL)
-    _check_tensor(fn, "weight", weight, shape=(D_MODEL,))
-    _check_tensor(fn, "bias", bias, shape=(D_MODEL,))
-    _check_eps(fn, "eps", eps)
-    _check_devices(fn, [("x", x), ("weight", weight), ("bias", bias)])
+    check_f32(fn, "x", x, width=D_MODEL)
+    check_f32(fn, "weight", weight, shape=(D_MODEL,))
+    check_f32(fn, "bias", bias, shape=(D_MODEL,))
+    check_number(fn, "eps", eps)
+    check_devices(fn, [("x", x), ("weight", weight), ("bias", bias)])
     x2 = _rows2d(x if x.dim() != 1 else x[None])
     if not x2.is_contiguous():
         x2 = x2.contiguous()
@@ -417,12 +382,8 @@ class HipEncoderLayer(nn.Module):
     @classmethod
     def adopt(cls, layer):
         """A HipEncoderLayer made of the very child modules of `layer` (same names, same order, same Parameter objects)."""
-        new = cls.__new__(cls)
-        nn.Module.__init__(new)
+        new = adopt(cls, layer)   # (layer holds no Parameters or buffers of its own: _is_encoder_layer)
         new.dim, new.nhead = D_MODEL // NHEAD, NHEAD
-        for name, child in layer._modules.items():
-            new._modules[name] = child
-        new.training = layer.training
         return new
 
     def forward(self, x, source):
@@ -467,13 +428,8 @@ def use_hip_encoder_layers(model):
     under the same names: state-dict keys, Parameter objects, optimiser state and checkpoints do not change.  Layers with biases,
     other widths or 'full' attention are left alone.  Composes with the other use_hip_* calls in any order.  Returns the number of
     registrations swapped; a second call finds none."""
-    swapped = 0
-    made = {}   # a module registered under several parents stays ONE module
-    for parent in list(model.modules()):
-        for name, child in list(parent._modules.items()):
-            if child is not None and _is_encoder_layer(child):
-                if id(child) not in made:
-                    made[id(child)] = (child, HipEncoderLayer.adopt(child))   # (the old module is kept alive: its id stays its own)
-                parent._modules[name] = made[id(child)][1]
-                swapped += 1
-    return swapped
+    def make(m):
+        if _is_encoder_layer(m):
+            return HipEncoderLayer.adopt(m)
+
+    return swap_modules(model, make)

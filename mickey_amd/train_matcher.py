@@ -20,6 +20,7 @@ import numbers
 import torch
 
 from . import ops
+from ._train_common import check_f32, swap_modules
 
 
 def _is_split(C, temperature, split):
@@ -27,49 +28,50 @@ def _is_split(C, temperature, split):
         return ops.dual_softmax_split_ok(C, temperature)
     if split is True or split is False:
         if split and not ops.dual_softmax_split_ok(C, temperature):
-            raise ValueError("split=True needs C == 128 and temperature >= log2(e) / 100 (mk_dual_softmax_split), got C=%d, "
-                             "temperature=%g" % (C, temperature))
+            raise ValueError("dual_softmax_train: split=True needs C == 128 and temperature >= log2(e) / 100 (mk_dual_softmax_split), "
+                             "got C=%d, temperature=%g" % (C, temperature))
         return split
-    raise ValueError("split must be 'auto', True or False, got %r" % (split,))
+    raise ValueError("dual_softmax_train: split must be 'auto', True or False, got %r" % (split,))
+
+
+_FN = "dual_softmax_train"
 
 
 def _check_f32_device(name, t, dev):
-    if not torch.is_tensor(t):
-        raise ValueError("%s must be a tensor, got %s" % (name, type(t).__name__))
-    if t.dtype != torch.float32:
-        raise ValueError("%s must be float32, got %s" % (name, t.dtype))
-    if not t.is_cuda or (dev is not None and t.device != dev):
-        raise ValueError("%s must be a device tensor on %s, got %s" % (name, dev if dev is not None else "the GPU", t.device))
+    check_f32(_FN, name, t)
+    if not t.is_cuda or (dev is not None and t.device != dev):   # (kept here: for this op a CPU tensor is a ValueError, not check_devices' MickeyHipError)
+        raise ValueError("%s: %s must be a device tensor on %s, got %s" % (_FN, name, dev if dev is not None else "the GPU", t.device))
 
 
 def _validate(dsc0, dsc1, scr0, scr1, temperature, dustbin):
     """Every check of dual_softmax_train, on the host, before anything is launched: raises ValueError."""
     for name, d in (("dsc0", dsc0), ("dsc1", dsc1)):
         if not torch.is_tensor(d) or d.dim() != 3:
-            raise ValueError("%s must be a [B, C, n] tensor, got %s" % (name, tuple(d.shape) if torch.is_tensor(d) else type(d).__name__))
+            raise ValueError("%s: %s must be a [B, C, n] tensor, got %s" % (_FN, name, tuple(d.shape) if torch.is_tensor(d) else type(d).__name__))
     B, C, n0 = dsc0.shape
     if dsc1.shape[0] != B or dsc1.shape[1] != C:
-        raise ValueError("dsc0 %s and dsc1 %s must share B and C" % (tuple(dsc0.shape), tuple(dsc1.shape)))
+        raise ValueError("%s: dsc0 %s and dsc1 %s must share B and C" % (_FN, tuple(dsc0.shape), tuple(dsc1.shape)))
     n1 = dsc1.shape[2]
     if B < 1 or n0 < 1 or n1 < 1:
-        raise ValueError("empty descriptors: dsc0 %s, dsc1 %s" % (tuple(dsc0.shape), tuple(dsc1.shape)))
+        raise ValueError("%s: empty descriptors: dsc0 %s, dsc1 %s" % (_FN, tuple(dsc0.shape), tuple(dsc1.shape)))
     if C != 128:
-        raise ValueError("the HIP matcher backward needs C == 128 descriptor channels, got %d" % C)
+        raise ValueError("%s: the HIP matcher backward needs C == 128 descriptor channels, got %d" % (_FN, C))
     _check_f32_device("dsc0", dsc0, None)
     _check_f32_device("dsc1", dsc1, dsc0.device)
     if (scr0 is None) != (scr1 is None):
-        raise ValueError("scr0 and scr1 go together (keypoint scores of both images, or neither)")
+        raise ValueError("%s: scr0 and scr1 go together (keypoint scores of both images, or neither)" % _FN)
     if scr0 is not None:
         for name, s, n in (("scr0", scr0, n0), ("scr1", scr1, n1)):
             if not torch.is_tensor(s) or s.numel() != B * n or tuple(s.shape) not in ((B, n), (B, 1, n)):
-                raise ValueError("%s must be [%d, %d] or [%d, 1, %d], got %s" %
-                                 (name, B, n, B, n, tuple(s.shape) if torch.is_tensor(s) else type(s).__name__))
+                raise ValueError("%s: %s must be [%d, %d] or [%d, 1, %d], got %s" %
+                                 (_FN, name, B, n, B, n, tuple(s.shape) if torch.is_tensor(s) else type(s).__name__))
             _check_f32_device(name, s, dsc0.device)
+    # (kept here: a bool passes as a temperature, as it always has; check_number refuses one)
     if not isinstance(temperature, numbers.Real) or not math.isfinite(float(temperature)) or float(temperature) <= 0:
-        raise ValueError("temperature must be a finite positive number, got %r" % (temperature,))
+        raise ValueError("%s: temperature must be a finite positive number, got %r" % (_FN, temperature))
     if dustbin is not None and not isinstance(dustbin, numbers.Real):
         if not torch.is_tensor(dustbin) or dustbin.numel() != 1:
-            raise ValueError("dustbin must be None, a number or a one-element tensor, got %r" % (dustbin,))
+            raise ValueError("%s: dustbin must be None, a number or a one-element tensor, got %r" % (_FN, dustbin))
         _check_f32_device("dustbin", dustbin, dsc0.device)
     return B, C, n0, n1
 
@@ -155,16 +157,13 @@ def use_hip_matcher(model, split="auto"):
     """Replace every dual-softmax `matching_mat` inside `model` (a reference-style training model: featureMatcher.matching_mat,
     feature_matcher.py:13) by DualSoftmax, in place.  The dustbin_score Parameter OBJECT is kept, so optimiser state and
     checkpoints stay valid.  Returns the number of modules swapped."""
-    swapped = 0
-    for m in list(model.modules()):
-        old = getattr(m, "matching_mat", None)
+    def make(old):
         if not _is_dual_softmax(old):
-            continue
+            return None
         new = DualSoftmax({"TEMPERATURE": old.temperature, "USE_DUSTBIN": False}, split=split)
         if old.use_dustbin:
             new.dustbin_score = old.dustbin_score
             new.use_dustbin = True
-        new.train(old.training)
-        m.matching_mat = new
-        swapped += 1
-    return swapped
+        return new.train(old.training)
+
+    return swap_modules(model, make, name="matching_mat")

@@ -22,14 +22,14 @@ half precision (ValueError), double backward, hipGraph capture of a step, BatchN
 positional encoding, get_abs_kpts_coordinates, one launch across the four heads.
 """
 import inspect
-import math
 import numbers
 
 import torch
 from torch import nn
 from torch.autograd.function import once_differentiable
 
-from . import _native, ops
+from . import ops
+from ._train_common import adopt, aligned_copy, check_devices, check_f32, check_grad, check_number, is_number, is_real, swap_modules
 
 
 # ---- the tails as plain torch (any device, any float dtype) ---------------------------------------------------------------------
@@ -73,49 +73,19 @@ def desc_l2norm_formula(x, eps=1e-10):
 
 
 # ---- argument checks and layouts ---------------------------------------------------------------------------------------------
-def _check_number(fn, name, v, positive):
-    bad = isinstance(v, bool) or not isinstance(v, numbers.Real) or not math.isfinite(float(v))
-    if bad or (float(v) <= 0 if positive else float(v) < 0):
-        raise ValueError("%s: %s must be a finite %s number, got %r" % (fn, name, "positive" if positive else "non-negative", v))
-
-
 def _check_feat(fn, name, t):
-    if not torch.is_tensor(t):
-        raise ValueError("%s: %s must be a tensor, got %s" % (fn, name, type(t).__name__))
-    if t.dtype != torch.float32:
-        raise ValueError("%s: %s must be float32, got %s (autocast is not covered)" % (fn, name, t.dtype))
-    if t.dim() != 4:
-        raise ValueError("%s: %s must be [B, C, H, W], got %s" % (fn, name, tuple(t.shape)))
-    B, C, H, W = t.shape
+    check_f32(fn, name, t, rank=4, why=" ([B, C, H, W])")
+    C = t.shape[1]
     if C < ops.TAIL_MIN_C or C > ops.TAIL_MAX_C or C % 4:
         raise ValueError("%s: the width of %s must be a multiple of 4 in [%d, %d], got %d" % (fn, name, ops.TAIL_MIN_C, ops.TAIL_MAX_C, C))
-    if B < 1 or H < 1 or W < 1:
-        raise ValueError("%s: empty %s %s" % (fn, name, tuple(t.shape)))
-
-
-def _check_weight(fn, w, cout, C):
-    if not torch.is_tensor(w):
-        raise ValueError("%s: weight must be a tensor, got %s" % (fn, type(w).__name__))
-    if w.dtype != torch.float32:
-        raise ValueError("%s: weight must be float32, got %s (autocast is not covered)" % (fn, w.dtype))
-    if tuple(w.shape) != (cout, C, 1, 1):
-        raise ValueError("%s: weight must be %s (a bias-free 1x1 conv), got %s" % (fn, (cout, C, 1, 1), tuple(w.shape)))
-
-
-def _check_devices(fn, named):
-    if not all(t.is_cuda for _, t in named):
-        raise _native.MickeyHipError("%s needs device tensors (%s); mickey_amd has no CPU fallback"
-                                     % (fn, ", ".join("%s on %s" % (n, t.device) for n, t in named)))
-    if any(t.device != named[0][1].device for _, t in named):
-        raise ValueError("%s: tensors on different devices (%s)" % (fn, ", ".join("%s on %s" % (n, t.device) for n, t in named)))
 
 
 def _channels_last(x):
     """[B, C, H, W] -> the same values as a tensor whose [B H W, C] rows are dense and 16-byte aligned: x itself when it already is
     (channels_last memory, read in place), else one copy.  Differentiable."""
-    if x.permute(0, 2, 3, 1).is_contiguous() and x.data_ptr() % 16 == 0:
-        return x
-    return x.permute(0, 2, 3, 1).clone(memory_format=torch.contiguous_format).permute(0, 3, 1, 2)
+    rows = x.permute(0, 2, 3, 1)
+    copy = aligned_copy(rows)
+    return x if copy is rows else copy.permute(0, 3, 1, 2)
 
 
 def _rows(x4):
@@ -124,8 +94,7 @@ def _rows(x4):
 
 
 def _weight2d(w):
-    w2 = w.reshape(w.shape[0], w.shape[1])
-    return w2 if (w2.is_contiguous() and w2.data_ptr() % 16 == 0) else w2.clone(memory_format=torch.contiguous_format)
+    return aligned_copy(w.reshape(w.shape[0], w.shape[1]))
 
 
 class HeadTailFn(torch.autograd.Function):
@@ -152,8 +121,7 @@ class HeadTailFn(torch.autograd.Function):
         act, scale, temperature = ctx.cfg
         feat, weight = ctx.saved_tensors[:2]
         y = ctx.saved_tensors[2] if act != ops.TAIL_IDENTITY else None
-        if go.dtype != torch.float32:
-            raise ValueError("head tail backward: the incoming gradient must be float32, got %s" % go.dtype)
+        check_grad("head tail", go)
         B, C, H, W = feat.shape
         nf, nw = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         with torch.cuda.device(go.device):
@@ -180,8 +148,7 @@ class DescL2NormFn(torch.autograd.Function):
     @once_differentiable
     def backward(ctx, go):
         y, rnorm = ctx.saved_tensors
-        if go.dtype != torch.float32:
-            raise ValueError("desc_l2norm_train backward: the incoming gradient must be float32, got %s" % go.dtype)
+        check_grad("desc_l2norm_train", go)
         B, C, n = y.shape
         _, _, H, W = go.shape
         with torch.cuda.device(go.device):
@@ -191,8 +158,8 @@ class DescL2NormFn(torch.autograd.Function):
 
 def _tail(fn, feat, weight, cout, act, scale=1.0, border=0, temperature=1.0, eps=0.0):
     _check_feat(fn, "feat", feat)
-    _check_weight(fn, weight, cout, feat.shape[1])
-    _check_devices(fn, [("feat", feat), ("weight", weight)])
+    check_f32(fn, "weight", weight, shape=(cout, feat.shape[1], 1, 1), why=" (a bias-free 1x1 conv)")
+    check_devices(fn, [("feat", feat), ("weight", weight)])
     return HeadTailFn.apply(_channels_last(feat), weight, act, float(scale), int(border), float(temperature), float(eps))
 
 
@@ -207,8 +174,8 @@ def score_tail_train(feat, weight, border=3, use_softmax=True, temperature=100.0
     fn = "score_tail_train"
     if isinstance(border, bool) or not isinstance(border, numbers.Integral) or border < 0:
         raise ValueError("%s: border must be a non-negative integer, got %r" % (fn, border))
-    _check_number(fn, "temperature", temperature, True)
-    _check_number(fn, "eps", eps, False)
+    check_number(fn, "temperature", temperature, positive=True)
+    check_number(fn, "eps", eps)
     act = ops.TAIL_SOFTMAX if use_softmax else ops.TAIL_MASKED_SIGMOID
     return _tail(fn, feat, weight, 1, act, 1.0, int(border), temperature, eps)
 
@@ -223,7 +190,7 @@ def depth_tail_train(feat, weight, use_sigmoid=False, max_depth=60.0):
     with use_sigmoid; [B, 1, H, W]."""
     fn = "depth_tail_train"
     if use_sigmoid:
-        _check_number(fn, "max_depth", max_depth, True)
+        check_number(fn, "max_depth", max_depth, positive=True)
         return _tail(fn, feat, weight, 1, ops.TAIL_SIGMOID, max_depth)
     return _tail(fn, feat, weight, 1, ops.TAIL_IDENTITY)
 
@@ -233,8 +200,8 @@ def desc_l2norm_train(x, eps=1e-10):
     CONTIGUOUS, so that .view(B, C, H W) is the [B, C, n] tensor the matcher reads."""
     fn = "desc_l2norm_train"
     _check_feat(fn, "x", x)
-    _check_number(fn, "eps", eps, False)
-    _check_devices(fn, [("x", x)])
+    check_number(fn, "eps", eps)
+    check_devices(fn, [("x", x)])
     return DescL2NormFn.apply(_channels_last(x), float(eps))
 
 
@@ -250,19 +217,10 @@ class HipHead(nn.Module):
 
     @classmethod
     def adopt(cls, head, kind):
-        new = cls.__new__(cls)
-        nn.Module.__init__(new)
-        for name, child in head._modules.items():
-            new._modules[name] = child
-        for name, p in head._parameters.items():
-            new._parameters[name] = p
-        for name, b in head._buffers.items():
-            new._buffers[name] = b
-        new._non_persistent_buffers_set = set(head._non_persistent_buffers_set)
+        new = adopt(cls, head)
         for name in _ATTRS:
             if name in head.__dict__:
                 setattr(new, name, head.__dict__[name])
-        new.training = head.training
         new.kind = kind
         new.block4_takes_relu = _takes_relu(head.resblock4)
         # the detector's eps Parameter, read once here: no .item() per step
@@ -298,10 +256,6 @@ def _is_tail_conv(m, cout):
             and ops.TAIL_MIN_C <= m.in_channels <= ops.TAIL_MAX_C and m.in_channels % 4 == 0)
 
 
-def _is_number(v, positive=False):
-    return (not isinstance(v, bool) and isinstance(v, numbers.Real) and math.isfinite(float(v)) and (float(v) > 0 or not positive))
-
-
 def _head_kind(m):
     """'score' / 'offset' / 'depth' / 'desc' for a module with the structure of one of the reference's heads, by attributes and not by
     class; None for anything else."""
@@ -312,12 +266,12 @@ def _head_kind(m):
         return None
     kinds = []
     d = m.__dict__
-    if "score" in mods and _is_tail_conv(mods["score"], 1) and isinstance(d.get("use_softmax"), bool) and _is_number(d.get("tmp_softmax"), True):
+    if "score" in mods and _is_tail_conv(mods["score"], 1) and isinstance(d.get("use_softmax"), bool) and is_number(d.get("tmp_softmax"), True):
         kinds.append("score")
     if "xy_offset" in mods and _is_tail_conv(mods["xy_offset"], 2):
         kinds.append("offset")
     if ("depth" in mods and _is_tail_conv(mods["depth"], 1) and isinstance(d.get("use_depth_sigmoid"), bool)
-            and _is_number(d.get("max_depth"), bool(d.get("use_depth_sigmoid")))):
+            and is_real(d.get("max_depth")) and (d["max_depth"] > 0 or not d["use_depth_sigmoid"])):   # (unused without the sigmoid: any sign)
         kinds.append("depth")
     if isinstance(d.get("norm_desc"), bool):
         kinds.append("desc")
@@ -337,14 +291,9 @@ def use_hip_tails(model):
     not change; only forward differs.  The detector's eps is read once, here.  Convs with a bias, other widths and norm_desc == False
     are left alone.  Composes with the other use_hip_* calls in any order.  Returns the number of heads swapped; a second call finds
     none."""
-    swapped = 0
-    made = {}   # a module registered under several parents stays ONE module
-    for parent in list(model.modules()):
-        for name, child in list(parent._modules.items()):
-            kind = _head_kind(child) if child is not None else None
-            if kind is not None:
-                if id(child) not in made:
-                    made[id(child)] = (child, HipHead.adopt(child, kind))   # (the old module is kept alive: its id stays its own)
-                parent._modules[name] = made[id(child)][1]
-                swapped += 1
-    return swapped
+    def make(m):
+        kind = _head_kind(m)
+        if kind is not None:
+            return HipHead.adopt(m, kind)
+
+    return swap_modules(model, make)
