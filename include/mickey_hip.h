@@ -142,7 +142,8 @@ int mk_gemm_qkv_ln(const void* A, int lda, const void* W, int ldw, const float* 
  * w + g*D, b + g*D (the four heads normalised in one launch).
  * bord_h > 0: `out` is a stack of BORDERED feature maps (below, mk_bordered_rows) of bord_m = nimg * bord_h * bord_w pixels
  * each: output row r goes to row (r / bord_m) * mk_bordered_rows(nimg, bord_h, bord_w) + bordered(r % bord_m).  The
- * border rows are not written.  bord_h = 0: dense rows. */
+ * border rows are not written.  bord_h = 0: dense rows.  ldx, ldo, ldr: multiples of 4 and >= D (ldo / ldr of a null out /
+ * resid are not looked at beyond the multiple). */
 int mk_layernorm(const float* x, int ldx, const float* w, const float* b, float eps, void* out, int ldo, int out_is_f32,
                  float* resid, int ldr, int rows_out, int D, int rows_per_img, int skip, int wgroup_rows, int bord_h,
                  int bord_w, int bord_m, int dtype, mk_stream_t stream);
@@ -318,7 +319,7 @@ int mk_posenc_add(const void* x, const float* pe, float* xs, void* cat, int ld_c
 long long mk_linattn_work_floats(int groups, int nimg, int L, int C);
 int mk_linattn_kv(const float* qkv, float* kv, float* work, int groups, int nimg, int L, int C, mk_stream_t stream);
 /* Step 2: msg[s, h*16+v] = (phi(q_s) . KV[:, v]) * L / (phi(q_s) . Ksum + 1e-6), written lp to
- * out [G][nimg*L, ldo]. */
+ * out [G][nimg*L, ldo].  C % 16 == 0, C <= 128 (what mk_linattn_kv can produce kv for), ldo % 8 == 0, ldo >= C. */
 int mk_linattn_apply(const float* qkv, const float* kv, void* out, int ldo, int groups, int nimg, int L, int C, int dtype,
                      mk_stream_t stream);
 
@@ -461,7 +462,8 @@ int mk_train_desc_l2norm_bwd(const float* g, const float* y, const float* rnorm,
  *   scr   [nimg, h*w]      border-masked temperature-100 softmax (or sigmoid) of w_score . feat_det
  *   kps   [nimg, 2, h*w]   (sigmoid(w_xy . feat_off) + cell) * down   (x row, then y row)
  *   depth [nimg, h*w]      w_depth . feat_depth  (max_depth * sigmoid(.) if use_depth_sigmoid)
- *   dsc   [nimg, Cd, h*w]  feat_dsc / sqrt(sum_c feat_dsc^2 + 1e-10) if norm_dsc, transposed */
+ *   dsc   [nimg, Cd, h*w]  feat_dsc / sqrt(sum_c feat_dsc^2 + 1e-10) if norm_dsc, transposed
+ * h * w + 32 floats and Cd * 65 floats of LDS, each up to 160 KiB (reserved on the first call). */
 int mk_head_tails(const float* feat_det, const float* w_score, const float* feat_off, const float* w_xy,
                   const float* feat_depth, const float* w_depth, const float* feat_dsc, float* scr, float* kps, float* depth,
                   float* dsc, int nimg, int h, int w, int C, int Cd, int border, int use_softmax, int use_depth_sigmoid,

@@ -306,6 +306,15 @@ int mk_head_tails(const float* feat_det, const float* w_score, const float* feat
   MK_CHECK_ARG(nimg > 0 && n > 0 && C > 0 && Cd > 0 && (size_t)(n + 32) * 4 <= 160 * 1024 && Cd * 65 * 4 <= 160 * 1024,
                "mk_head_tails: bad geometry");
   hipStream_t st = (hipStream_t)stream;
+  {  // det_norm_kernel and dsc_tail_kernel take up to the 160 KiB admitted above: past 64 KiB a launch needs the attribute
+    static bool done = false;
+    if (!done) {
+      hipError_t e = hipFuncSetAttribute((const void*)det_norm_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+      if (e == hipSuccess) e = hipFuncSetAttribute((const void*)dsc_tail_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+      if (e != hipSuccess) { mk_set_error("mk_head_tails: cannot reserve %d B of LDS: %s", 160 * 1024, hipGetErrorString(e)); return MK_ERR_LAUNCH; }
+      done = true;
+    }
+  }
   hipLaunchKernelGGL(kp_depth_tail_kernel, dim3((unsigned)(((long long)nimg * n + 3) / 4)), dim3(256), 0, st, feat_det, w_score,
                      feat_off, w_xy, feat_depth, w_depth, scr, kps, depth, nimg, h, w, C, use_depth_sigmoid, max_depth, down);
   MK_CHECK_LAUNCH();

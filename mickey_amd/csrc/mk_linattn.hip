@@ -696,8 +696,8 @@ int mk_linattn_kv(const float* qkv, float* kv, float* work, int groups, int nimg
 int mk_linattn_apply(const float* qkv, const float* kv, void* out, int ldo, int groups, int nimg, int L, int C, int dtype,
                      mk_stream_t stream) {
   const int H = C / 16;
-  MK_CHECK_ARG(qkv && kv && out && groups > 0 && nimg > 0 && L > 0 && C % 16 == 0 && H <= 64 && ldo % 8 == 0 && ldo >= C,
-               "mk_linattn_apply: bad args");
+  MK_CHECK_ARG(qkv && kv && out && groups > 0 && nimg > 0 && L > 0 && C > 0 && C % 16 == 0 && C <= 128 && ldo % 8 == 0 && ldo >= C,
+               "mk_linattn_apply: bad args (C <= 128, as mk_linattn_kv)");
   const int tpb = 256 / H;
   dim3 grid((L + tpb - 1) / tpb, groups * nimg);
   const size_t lds = block_bytes(C);

@@ -476,6 +476,8 @@ static int layernorm_launch(const float* x, int ldx, const float* w, const float
                LN_MAXV * 256);
   MK_CHECK_ARG(rows_out > 0 && rows_per_img > skip && skip >= 0 && ldx % 4 == 0 && ldo % 4 == 0 && ldr % 4 == 0,
                "mk_layernorm: bad geometry");
+  MK_CHECK_ARG(ldx >= D && (!out || ldo >= D) && (!resid || ldr >= D),
+               "mk_layernorm: leading dimensions (ldx=%d ldo=%d ldr=%d) must be >= D=%d", ldx, ldo, ldr, D);
   if (D <= 128) {
     dim3 gridn((rows_out + 8 * LNN_TRIPS - 1) / (8 * LNN_TRIPS));
 #define MK_LNN(T_)                                                                                                         \

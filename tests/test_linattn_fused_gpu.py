@@ -1,7 +1,9 @@
 """-m gpu: the heads' linear attention with its projections inside (mk_linattn_kv_fused, mk_linattn_apply_fused) against the
 launches it replaces -- mk_gemm_grouped (fp32 q | k | v) -> mk_linattn_kv -> mk_linattn_apply -> mk_gemm_ln128 -- on the same
 inputs.  The fused kernels compute the same accumulators and sum everything in the same order: every comparison is torch.equal.
-Shapes: L = 35 (one ragged chunk), L = 99 = 64 + 35 (a ragged second chunk whose last 16-row block holds 3 rows), L = 64 exactly."""
+Shapes: L = 35 (one ragged chunk), L = 99 = 64 + 35 (a ragged second chunk whose last 16-row block holds 3 rows), L = 64 exactly;
+and, sized from the device's CU count, enough images that a workgroup WALKS: `chunk += gridDim.x` of the kv kernel and
+`tile += step` of the apply kernel take further trips, each with its prefetch of the next chunk or tile."""
 import copy
 import math
 
@@ -25,8 +27,9 @@ def _dev():
 _CASES = {}
 
 
-def _case(G, nimg, gh, gw, dtype):
-    """Inputs and the unfused results of one case, computed once and shared (nothing below writes into them)."""
+def _case(G, nimg, gh, gw, dtype, keep=True):
+    """Inputs and the unfused results of one case, computed once and shared (nothing below writes into them).  keep = False: not
+    kept for later tests (the walking cases hold hundreds of MB)."""
     key = (G, nimg, gh, gw, dtype)
     if key in _CASES:
         return _CASES[key]
@@ -54,8 +57,10 @@ def _case(G, nimg, gh, gw, dtype):
     ops.gemm_ln128(msg, merge_w, lw, lb, 1e-5, out[:, :, C:], G, M, C, ldo=2 * C)
     torch.cuda.synchronize()
     assert bool(torch.isfinite(kv).all()) and bool(torch.isfinite(work).all())
-    _CASES[key] = dict(cat=cat, qkv_w=qkv_w, merge_w=merge_w, lw=lw, lb=lb, kv=kv, work=work, msg=msg, out=out, L=L, M=M)
-    return _CASES[key]
+    c = dict(cat=cat, qkv_w=qkv_w, merge_w=merge_w, lw=lw, lb=lb, kv=kv, work=work, msg=msg, out=out, L=L, M=M)
+    if keep:
+        _CASES[key] = c
+    return c
 
 
 def _kv_fused(c, G, nimg, cat=None):
@@ -131,6 +136,63 @@ def test_fused_kernels_are_batch_invariant(dtype):
             ops.linattn_apply_fused(cat1, c["qkv_w"], kv1, cat1[:, :, C:], G, 1, L, C, **kw)
             ref = (c["out"][:, :, C:] if merge else c["msg"])[:, i * L:(i + 1) * L]
             assert torch.equal(cat1[:, :, C:], ref), (i, merge)
+
+
+# ---- the walk loops: shapes from the CU count, the trip counts asserted from the launch rules of mk_linattn.hip ----------------------
+def _cus():
+    _dev()
+    return torch.cuda.get_device_properties(0).multi_processor_count
+
+
+def _kv_trips(gi, L):
+    """chunks each workgroup of an image walks: per_img = min(ceil(8 CUs / gi), nchunk) workgroups, chunk += per_img"""
+    nchunk = (L + 63) // 64
+    per_img = min((8 * _cus() + gi - 1) // gi, nchunk)
+    return [len(range(b, nchunk, per_img)) for b in range(per_img)]
+
+
+def _apply_trips(gi, L):
+    """16-token tiles each (workgroup, wave) of an image walks: per_img = min(ceil(CUs / gi), ceil(L / 128)), tile += 8 per_img"""
+    ntile = (L + 15) // 16
+    per_img = min((_cus() + gi - 1) // gi, (L + 127) // 128)
+    return [[len(range(b * 8 + wv, ntile, per_img * 8)) for wv in range(8)] for b in range(per_img)]
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("per_cu", [8, 4])
+def test_kv_fused_walks_its_chunks(per_cu, dtype):
+    """L = 131 = 64 + 64 + 3.  gi = 8 CUs: one workgroup per image walks all 3 chunks, the last ragged (both branches of the prefetch:
+    the chunk's next token set, the next chunk's first).  gi = 4 CUs: two workgroups per image walk 2 chunks and 1 chunk."""
+    G, nimg, L = 1, per_cu * _cus(), 131
+    assert _kv_trips(G * nimg, L) == ([3] if per_cu == 8 else [2, 1])
+    c = _case(G, nimg, 1, L, dtype, keep=False)
+    kv, work = _kv_fused(c, G, nimg)
+    assert torch.equal(work, c["work"])
+    assert torch.equal(kv, c["kv"])
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("halves,L", [(2, 131), (1, 300)])
+def test_apply_fused_walks_its_tiles(halves, L, dtype):
+    """gi = CUs, L = 131: one workgroup per image, 9 sixteen-token tiles, wave 0 takes two.  gi = CUs / 2, L = 300: two workgroups
+    per image, 19 tiles, waves 0 .. 2 of the first take two.  With and without merge_w."""
+    G = 2
+    nimg = halves * _cus() // 4
+    assert G * nimg == halves * _cus() // 2
+    trips = _apply_trips(G * nimg, L)
+    if halves == 2:
+        assert trips == [[2, 1, 1, 1, 1, 1, 1, 1]]
+    else:
+        assert trips == [[2, 2, 2, 1, 1, 1, 1, 1], [1] * 8] and (L + 15) // 16 == 19
+    from mickey_amd import ops
+    c = _case(G, nimg, 1, L, dtype, keep=False)
+    for merge in (True, False):
+        buf, cat = _padded(c, G)
+        kw = dict(merge_w=c["merge_w"], ln_w=c["lw"], ln_b=c["lb"]) if merge else {}
+        ops.linattn_apply_fused(cat, c["qkv_w"], c["kv"], cat[:, :, C:], G, nimg, L, C, **kw)
+        assert torch.equal(cat[:, :, C:], c["out"][:, :, C:] if merge else c["msg"]), merge
+        assert torch.equal(cat[:, :, :C], c["cat"][:, :, :C])
+        assert bool((buf[:, :2] == SENTINEL).all()) and bool((buf[:, -2:] == SENTINEL).all())
 
 
 def test_heads_forward_fused_equals_unfused(cfg):
