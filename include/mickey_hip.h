@@ -277,7 +277,12 @@ int mk_absmax_scale(const float* x, int d0, int d1, int d2, int d3, long long s0
 /* Operand planes of a training conv (utils/extractor_utils.py:18-31).  A plane buffer is a zero-initialised fp16 matrix of
  * mk_conv_train_plane_rows(nimg, H, Wd) rows whose row mk_conv_train_lead_rows(Wd) is row 0 of the bordered feature map: the
  * weight-gradient kernel sweeps whole K steps of 32 rows with one row shift per tap and no bounds test, so Wd + 2 rows in front
- * of the map and the rows behind it up to the buffer's end must exist and be zero.  hi / lo point at bordered row 0.
+ * of the map and the rows behind it up to the buffer's end must exist.  What they must hold depends on the operand: in gY's
+ * buffers the rows behind the map must be zero, like its border rows (they are summed; the rows in front are never read); in X's
+ * buffers the rows in front of and behind the map only ever meet zero rows of gY and need to be FINITE, no more (an Inf or NaN
+ * times zero would reach dw), and likewise gY's columns Cout .. ldg - 1, whose results are dropped.  A zero-initialised buffer
+ * (ops.conv_train_plane_buffer) satisfies all of it; tests/test_conv_edges_gpu.py holds dw bit-identical between zero and finite
+ * non-zero fillings.  hi / lo point at bordered row 0.
  * mk_conv_train_planes: fp32 [nimg, C, H, Wd] with element strides (contiguous, channels_last, sliced ...) -> x * scale[0] = hi +
  * lo, [.., ld] fp16 (no clamping: an Inf gives Inf / NaN planes); C % 4 == 0, ld % 4 == 0, ld >= C; columns C .. ld - 1 and all
  * border rows are left alone. */
