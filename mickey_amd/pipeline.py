@@ -102,24 +102,24 @@ def encoder_forward(W, ws, img):
     token matrix, no concatenated copy of the images).  Returns the final-norm patch tokens, lp, as a bordered feature map
     of nimg gh x gw grids."""
     x, nimg, gh, gw = _encoder_trunk(W, ws, img)
-    dev, lp, D = x.device, W.lp, W.D
+    dev, D = x.device, W.D
     npatch = gh * gw
     ntok = npatch + 1
     # the heads' operand type, as a BORDERED feature map (mickey_hip.h: what a 3x3 conv reads; border rows stay zero)
     # (bordered buffers are zeroed ONCE and only their pixel rows are ever written: the key carries the geometry, because two
     # geometries can share a row count while their border rows sit elsewhere)
     R = ops.bordered_rows(nimg, gh, gw)
-    if getattr(W, "heads_split", False):
+    if W.heads_split:
         # split-operand heads: the final norm writes the convs' (hi, lo) fp16 operand planes directly (no fp32 feature map).
         # features_lp (AMD.FEATURES_LP; automatic behind an fp16 encoder): the reference's heads receive what its fp16 encoder
         # returns -- fp16 values, widened exactly by .float() (mickey_extractor.py:49-52) -- so only the hi plane is written (the rows
         # rounded to fp16) and the lo plane of this buffer, zeroed at allocation, stays zero: the first conv of every head then runs
         # two products instead of three (heads_forward)
-        flp = bool(getattr(W, "features_lp", False))
+        flp = W.features_lp
         feat = ws.get_planes("feat_hl%s_%d_%d_%d" % ("_lp" if flp else "", nimg, gh, gw), (R, D), dev, zero=True)
     else:
-        feat = ws.get("feat_%d_%d_%d" % (nimg, gh, gw), (R, D), getattr(W, "lp_heads", lp), dev, zero=True)
-    hi_only = isinstance(feat, tuple) and bool(getattr(W, "features_lp", False))
+        feat = ws.get("feat_%d_%d_%d" % (nimg, gh, gw), (R, D), W.lp_heads, dev, zero=True)
+    hi_only = W.heads_split and W.features_lp
     ops.layernorm(x, W.norm_w, W.norm_b, 1e-6, out=(feat[0], None) if hi_only else feat, rows_out=nimg * npatch, rows_per_img=ntok, skip=1,
                   bordered=(nimg, gh, gw), sat=ws.sat_flag)
     return feat, gh, gw
@@ -139,174 +139,170 @@ def encoder_features(W, ws, img, round_fp16=False):
     return out
 
 
+# ---- the heads ("The heads' host code": what an activation is, the stride rules of the helpers, the launch record) ----
+def _t(x):   # the tensor that carries the shape and strides of an activation (a tensor, or the (hi, lo) pair of its fp16 planes)
+    return x[0] if isinstance(x, tuple) else x
+
+
+def _sub(x, idx):   # x[idx] of an activation (of both planes)
+    return tuple(p[idx] for p in x) if isinstance(x, tuple) else x[idx]
+
+
+def _wscale(w):   # power-of-two scale of a split weight tensor's planes (set by weights.prepare on the tensor object)
+    if getattr(w, "mk_scale", None) is None:
+        raise RuntimeError("split-operand weight without its plane scale: the tensor is not the one weights.prepare made "
+                           "(copied / moved weights must be re-prepared)")
+    return w.mk_scale
+
+
+def _bordered(W, ws, name, lead, C, grid, dev):
+    """A bordered activation [*lead, bordered_rows, C] for a 3x3 conv to read (zeroed once; its key carries the geometry)."""
+    shape, geo = tuple(lead) + (ops.bordered_rows(*grid), C), "_%d_%d_%d" % grid
+    if W.heads_split:
+        return ws.get_planes(name + "_hl" + geo, shape, dev, zero=True)
+    return ws.get(name + geo, shape, W.lp_heads, dev, zero=True)
+
+
+def _conv(x, w, bias, out, grid, act, short=None, has_sc=True, either=False, bordered=False, sat=None):
+    """One 3x3 conv launch on grid = (nimg, gh, gw): out = act(conv(x, w) + bias + shortcut), out bordered or dense rows.
+    short: the block input, carried by shortcut columns of w (has_sc: as in2) or added as it is (resid); either: a block that
+    exists in both forms states the shortcut's stride for both."""
+    def gs(t, grouped=3):   # [groups, rows, cols] (bias: [groups, cols]): .stride(0); no group dimension: 0 = shared by all groups
+        return t.stride(0) if t is not None and t.dim() == grouped else 0
+    xt, st = _t(x), _t(short)
+    kw = dict(act=act, stride_in1=gs(xt), stride_w=gs(w), stride_bias=gs(bias, 2), stride_out=gs(_t(out)), out_bordered=bordered)
+    if short is not None:
+        kw.update(in2=short if has_sc else None, C2=st.shape[-1], stride_in2=gs(st))
+    args = (xt.shape[-1], w, bias, out, w.shape[-2], w.shape[0] if w.dim() == 3 else 1) + tuple(grid)
+    if isinstance(x, tuple):
+        return ops.conv3x3_split(x, *args, w_scale=_wscale(w), sat=sat, **kw)
+    if either:
+        kw.update(resid=None if has_sc else short, stride_resid=gs(st))
+    return ops.conv3x3(x, *args, **kw)
+
+
+def _basic_block(x, blk, h, out, grid, sat, act=ops.ACT_RELU, bordered=False, hi_only=False, rb4=False):
+    """BasicBlock (BatchNorm folded): conv -> ReLU -> h (bordered) -> conv + shortcut of x -> act -> out.  In split mode the
+    epilogues write the next conv's operand planes directly (no fp32 round trip, no mk_split_planes pass).  hi_only: x's lo
+    plane is identically zero -- the first conv reads the hi plane alone, two products instead of three.  rb4: shortcut columns
+    or an identity shortcut by the checkpoint (blk.has_sc), and an fp32 output in front of the tails: no saturation word."""
+    _conv((x[0], None) if hi_only else x, blk.w1, blk.b1, h, grid, ops.ACT_RELU, bordered=True, sat=sat)
+    return _conv(h, blk.w2, blk.b2, out, grid, act, short=x, has_sc=blk.has_sc if rb4 else True, either=rb4, bordered=bordered,
+                 sat=None if rb4 else sat)
+
+
+def _linear(a, w, out, act=ops.ACT_NONE, sat=None):
+    """out[g] = act(a[g] @ w[g]^T): a [G, M, K] (a column block of wider rows: its own row stride and pointer), w [G, N, K]
+    (split: 2 K interleaved (hi | lo) columns, weights.split_conv_weight), out [G, M, N]; a / out tensors or plane pairs."""
+    at, ot = _t(a), _t(out)
+    G, M, N = at.shape[0], at.shape[1], w.shape[1]
+    if isinstance(a, tuple):
+        return ops.gemm_grouped_split(a, w, None, out, G, M, N, w.shape[2] // 2, at.stride(1), ot.stride(1), at.stride(0),
+                                      w.stride(0), 0, ot.stride(0), act=act, w_scale=_wscale(w), sat=sat)
+    return ops.gemm_grouped(a, w, None, out, G, M, N, w.shape[2], at.stride(1), w.stride(1), ot.stride(1), at.stride(0),
+                            w.stride(0), 0, ot.stride(0), act=act)
+
+
+def _conv_stack(W, ws, feat, grid):
+    """resblock1-3 of the four heads (groups: det_head, det_offset, depth_head, dsc_head), all reading one feature map.
+    -> dense rows [4, nimg * gh * gw, C] of the heads' type: what the row-wise attention kernels read."""
+    x, dev, last = feat, _t(feat).device, len(W.rb) - 1
+    for bi, rb in enumerate(W.rb):
+        G, co = rb.w1.shape[:2]
+        h = _bordered(W, ws, "rb%d_h" % bi, (G,), co, grid, dev)
+        out = _bordered(W, ws, "rb%d_x" % bi, (G,), co, grid, dev) if bi < last else \
+            ws.get("rb%d_x_%d_%d_%d" % ((bi,) + grid), (G, grid[0] * grid[1] * grid[2], co), W.lp_heads, dev)
+        x = _basic_block(x, rb, h, out, grid, ws.sat_flag, bordered=bi < last, hi_only=bi == 0 and W.features_lp)
+    return x
+
+
+def _position_encoding(W, ws, x, grid, cfg):
+    """x [G, M, C] -> (xs fp32 [G, M, C]: the layers' residual stream, cat lp [G, M, 2C]: x (+ pe) in its left half).  The
+    keypoint heads (groups 0-2) and the descriptor head take the sine table or not by their own switches: two launches then."""
+    G, M, C = x.shape
+    xs = ws.get("att_xs", (G, M, C), torch.float32, x.device)
+    cat = ws.get("att_cat", (G, M, 2 * C), W.lp_heads, x.device)
+    pe = wts_mod.sine_pos_table(W, C, grid[1], grid[2], x.device)
+    kp_pe, dsc_pe = bool(cfg["MICKEY"]["KP_HEADS"]["POS_ENCODING"]), bool(cfg["MICKEY"]["DSC_HEAD"]["POS_ENCODING"])
+    for sl, on in [(slice(None), kp_pe)] if kp_pe == dsc_pe else [(slice(0, 3), kp_pe), (slice(3, None), dsc_pe)]:
+        ops.posenc_add(x[sl], pe if on else None, xs[sl], cat[sl], x[sl].shape[0], grid[0], pe.shape[0], C)
+    return xs, cat
+
+
+def _attention_layers(W, ws, xs, cat, grid, cfg):
+    """Transformer_self_att: the linear-attention encoder layers, residual stream xs in fp32.  -> the bordered activation
+    [G, bordered_rows, C] that resblock4's convs read, written by the last layer's closing LayerNorm."""
+    nimg, L = grid[0], grid[1] * grid[2]
+    G, M, C = xs.shape
+    dev, lp, split, sat = xs.device, W.lp_heads, W.heads_split, ws.sat_flag
+    left, right = (Ellipsis, slice(0, C)), (Ellipsis, slice(C, None))   # cat's column halves: the layer input | norm1(message)
+    # 16-bit operands: Linear(-> 128) + LayerNorm (+ residual) in one pass (mk_gemm_ln128), and with AMD.LINATTN_FUSED q | k | v are
+    # projected inside the attention kernels (no fp32 qkv rows, no msg rows); off = the separate launches, the same bits (A/B runs)
+    ln128 = not split and C == 128 and lp != torch.float32
+    fused = ln128 and bool(cfg["AMD"].get("LINATTN_FUSED", True))
+    kv = ws.get("att_kv", (G * nimg * (C // 16), 272), torch.float32, dev)
+    kvw = ws.get("att_kvw", (ops.linattn_work_floats(G, nimg, L, C),), torch.float32, dev)
+    qkv, msg = (None, None) if fused else (ws.get("att_qkv", (G, M, 3 * C), torch.float32, dev), ws.get("att_msg", (G, M, C), lp, dev))
+    mrg, hid = ws.get("att_mrg", (G, M, C), torch.float32, dev), ws.get("att_hid", (G, M, 2 * C), lp, dev)
+    out = _bordered(W, ws, "att_out", (G,), C, grid, dev)
+    # c, m, h: the operand forms of cat / msg / hid.  split: the layers' small linears on split operands too (fp32 MFMA: 4.9 ms per
+    # 32 pairs; split: the conversions below + 12 HBM-bound GEMMs) -- planes of `cat` (its two column halves are rewritten at
+    # different times), of `msg`, and `hid` written as planes by the GEMM that produces it
+    c, m, h = cat, msg, hid
+    if split:
+        c, m, h = (ws.get_planes("att_%s_hl" % nm, t.shape, dev) for nm, t in (("cat", cat), ("msg", msg), ("hid", hid)))
+    for li, lay in enumerate(W.att):
+        if fused:
+            ops.linattn_kv_fused(cat, lay.qkv_w, kv, kvw, G, nimg, L, C)
+            ops.linattn_apply_fused(cat, lay.qkv_w, kv, cat[right], G, nimg, L, C, merge_w=lay.merge_w, ln_w=lay.n1w, ln_b=lay.n1b)
+        else:   # the separate launches; split: the same on plane operands, behind a conversion of what an fp32 kernel wrote
+            if split and li == 0:   # (later layers: the previous layer's closing LayerNorm wrote these planes)
+                ops.split_planes(cat[left], *_sub(c, left), sat=sat)
+            _linear(_sub(c, left), lay.qkv_w, qkv, sat=sat)
+            ops.linattn_kv(qkv, kv, kvw, G, nimg, L, C)
+            ops.linattn_apply(qkv, kv, msg, msg.stride(1), G, nimg, L, C)
+            if split:
+                ops.split_planes(msg, *m, sat=sat)
+            if ln128:
+                ops.gemm_ln128(msg, lay.merge_w, lay.n1w, lay.n1b, 1e-5, cat[right], G, M, msg.shape[-1])
+            else:
+                _linear(m, lay.merge_w, mrg, sat=sat)
+                ops.layernorm(mrg, lay.n1w, lay.n1b, 1e-5, out=_sub(c, right), wgroup_rows=M, sat=sat)
+        _linear(c, lay.mlp0_w, h, act=ops.ACT_RELU, sat=sat)
+        # mlp[2] + norm2 + the layer's residual -> the next layer's input columns, or (last) resblock4's bordered input
+        o2, border = (out, grid) if li == len(W.att) - 1 else (_sub(c, left), None)
+        if ln128:
+            ops.gemm_ln128(hid, lay.mlp2_w, lay.n2w, lay.n2b, 1e-5, o2, G, M, hid.shape[-1], resid=xs, bordered=border)
+        else:
+            _linear(h, lay.mlp2_w, mrg, sat=sat)
+            ops.layernorm(mrg, lay.n2w, lay.n2b, 1e-5, out=o2, resid=xs, wgroup_rows=M, bordered=border, sat=sat)
+    return out
+
+
+def _resblock4(W, ws, x, grid):
+    """x: bordered [4, bordered_rows, C].  The three keypoint heads as one grouped block and the descriptor head as an ungrouped
+    one (no ReLU behind it: relu=False, mickey_extractor.py:246) -> fp32 dense rows f4 [3, M, ck], fd [M, cd]."""
+    kpw, dw, dev = W.rb4_kp, W.rb4_dsc, _t(x).device
+    assert not W.heads_split or (kpw.has_sc and dw.has_sc)   # (weights.prepare gives the descriptor block identity shortcut columns)
+    nk, M = kpw.w1.shape[0], grid[0] * grid[1] * grid[2]
+    f4, fd = ws.get("rb4_f", (nk, M, kpw.cout), torch.float32, dev), ws.get("rb4_fd", (M, dw.cout), torch.float32, dev)
+    h4, hd = _bordered(W, ws, "rb4_h", (nk,), kpw.cout, grid, dev), _bordered(W, ws, "rb4_hd", (), dw.cout, grid, dev)
+    _basic_block(_sub(x, slice(0, nk)), kpw, h4, f4, grid, ws.sat_flag, rb4=True)
+    return f4, _basic_block(_sub(x, nk), dw, hd, fd, grid, ws.sat_flag, act=ops.ACT_NONE, rb4=True)
+
+
 def heads_forward(W, ws, feat, nimg, gh, gw, cfg):
     """feat lp, bordered feature map of nimg gh x gw grids [bordered_rows, D] (split-operand heads: its (hi, lo) fp16 planes)
-    -> scr [nimg,1,n], kps [nimg,2,n]
-    (absolute pixels), depth [nimg,1,n], dsc [nimg,Cd,n], all fp32.  Every activation a 3x3 conv reads is bordered (zeroed
-    once at allocation, the kernels write pixels only); what only row-wise kernels read is dense."""
-    dev, lp = (feat[0] if isinstance(feat, tuple) else feat).device, getattr(W, "lp_heads", W.lp)
-    n = gh * gw
-    M = nimg * n
-    G = 4
-    mk = cfg["MICKEY"]
-    R = ops.bordered_rows(nimg, gh, gw)
-    geo = "_%d_%d_%d" % (nimg, gh, gw)   # bordered buffers: the workspace key carries the geometry (see encoder_forward)
-    split = bool(getattr(W, "heads_split", False))   # 3x3 convs on split fp16 operands inside the fp32 head pipeline
-    sat = ws.sat_flag   # the plane-writing kernels report saturation / NaN here (per workspace = per model: no shared word)
-
-    def wsc(w):   # power-of-two scale of a split weight tensor's planes (set by weights.prepare on the tensor object)
-        sc = getattr(w, "mk_scale", None)
-        if sc is None:
-            raise RuntimeError("split-operand weight without its plane scale: the tensor is not the one weights.prepare made "
-                               "(copied / moved weights must be re-prepared)")
-        return sc
-
-    def plane_pair(name, shape):
-        """Zeroed (hi, lo) fp16 planes of a bordered activation that a split conv WRITES (the next split conv's operands)."""
-        return ws.get_planes(name + "_hl" + geo, shape, dev, zero=True)
-
-    x_in, c_in, s_in = feat, W.D, 0   # first block: all four heads read the same feature map
-    xp = feat if split else None   # (the final norm wrote the planes)
-    for bi, rb in enumerate(W.rb):
-        co = rb.cout
-        last = bi == len(W.rb) - 1   # its output feeds the attention layers (row-wise kernels): dense rows
-        if split:
-            # conv -> conv inside the stack: the epilogue writes the next conv's (hi, lo) operand planes directly (no fp32
-            # round trip, no mk_split_planes pass); only the stack's output (read by the row-wise attention kernels) is fp32
-            hp = plane_pair("rb%d_h" % bi, (G, R, co))
-            # (the first block reads the feature map: with features_lp its lo plane is identically zero -- hi only, two products)
-            x1 = (xp[0], None) if bi == 0 and getattr(W, "features_lp", False) else xp
-            ops.conv3x3_split(x1, c_in, rb.w1, rb.b1, hp, co, G, nimg, gh, gw, act=ops.ACT_RELU, stride_in1=s_in, w_scale=wsc(rb.w1), sat=sat,
-                              stride_w=rb.w1.shape[1] * rb.w1.shape[2], stride_bias=co, stride_out=R * co, out_bordered=True)
-            xo = ws.get("rb%d_x" % bi + geo, (G, M, co), lp, dev) if last else plane_pair("rb%d_x" % bi, (G, R, co))
-            ops.conv3x3_split(hp, co, rb.w2, rb.b2, xo, co, G, nimg, gh, gw, act=ops.ACT_RELU, in2=xp, C2=c_in, w_scale=wsc(rb.w2), sat=sat,
-                              stride_in1=R * co, stride_in2=s_in, stride_w=rb.w2.shape[1] * rb.w2.shape[2], stride_bias=co,
-                              stride_out=(M if last else R) * co, out_bordered=not last)
-            if not last:
-                xp = xo
-        else:
-            h1 = ws.get("rb%d_h" % bi + geo, (G, R, co), lp, dev, zero=True)
-            xo = ws.get("rb%d_x" % bi + geo, (G, M if last else R, co), lp, dev, zero=not last)
-            ops.conv3x3(x_in, c_in, rb.w1, rb.b1, h1, co, G, nimg, gh, gw, act=ops.ACT_RELU, stride_in1=s_in,
-                        stride_w=rb.w1.shape[1] * rb.w1.shape[2], stride_bias=co, stride_out=R * co, out_bordered=True)
-            ops.conv3x3(h1, co, rb.w2, rb.b2, xo, co, G, nimg, gh, gw, act=ops.ACT_RELU, in2=x_in, C2=c_in,
-                        stride_in1=R * co, stride_in2=s_in, stride_w=rb.w2.shape[1] * rb.w2.shape[2], stride_bias=co,
-                        stride_out=(M if last else R) * co, out_bordered=not last)
-        x_in, c_in, s_in = xo, co, R * co
-    C = c_in  # 128
-    # ---- Transformer_self_att: 3 linear-attention encoder layers, residual stream in fp32 ----
-    xs = ws.get("att_xs", (G, M, C), torch.float32, dev)
-    cat = ws.get("att_cat", (G, M, 2 * C), lp, dev)
-    pe = wts_mod.sine_pos_table(W, C, gh, gw, dev)
-    kp_pe, dsc_pe = bool(mk["KP_HEADS"]["POS_ENCODING"]), bool(mk["DSC_HEAD"]["POS_ENCODING"])
-    if kp_pe == dsc_pe:
-        ops.posenc_add(x_in, pe if kp_pe else None, xs, cat, G, nimg, n, C)
-    else:
-        ops.posenc_add(x_in[:3], pe if kp_pe else None, xs[:3], cat[:3], 3, nimg, n, C)
-        ops.posenc_add(x_in[3:], pe if dsc_pe else None, xs[3:], cat[3:], 1, nimg, n, C)
-    # AMD.LINATTN_FUSED: q | k | v are projected inside the attention kernels (mk_linattn_*_fused: C = 128, 16-bit operands) -- no
-    # fp32 qkv rows, no msg rows; off = the separate launches (the same results bit for bit, for A/B runs)
-    fused_att = bool(cfg["AMD"].get("LINATTN_FUSED", True)) and not split and C == 128 and lp != torch.float32
-    kv = ws.get("att_kv", (G * nimg * (C // 16), 272), torch.float32, dev)
-    kvw = ws.get("att_kvw", (ops.linattn_work_floats(G, nimg, n, C),), torch.float32, dev)
-    if not fused_att:
-        qkv = ws.get("att_qkv", (G, M, 3 * C), torch.float32, dev)
-        msg = ws.get("att_msg", (G, M, C), lp, dev)
-    mrg = ws.get("att_mrg", (G, M, C), torch.float32, dev)
-    hid = ws.get("att_hid", (G, M, 2 * C), lp, dev)
-    if split:
-        x4 = None
-        x4h, x4l = plane_pair("att_out", (G, R, C))   # read by resblock4's convs: bordered planes, written by the last LayerNorm
-    else:
-        x4 = ws.get("att_out" + geo, (G, R, C), lp, dev, zero=True)   # read by resblock4's convs: bordered
-    nl = len(W.att)
-    if split:
-        # the layers' small linears on split operands too (fp32 MFMA: 4.9 ms per 32 pairs; split: the conversions below + 12
-        # HBM-bound GEMMs): planes of `cat` (its two column halves are rewritten at different times), of `msg`, and `hid`
-        # written as planes by the GEMM that produces it
-        catp = ws.get_planes("att_cat_hl", (G, M, 2 * C), dev)
-        msgp = ws.get_planes("att_msg_hl", (G, M, C), dev)
-        hidp = ws.get_planes("att_hid_hl", (G, M, 2 * C), dev)
-    for li, lay in enumerate(W.att):
-        last = li == nl - 1
-        if split:
-            if li == 0:   # later layers: the previous layer's closing LayerNorm wrote these planes
-                ops.split_planes(cat[:, :, :C], catp[0][:, :, :C], catp[1][:, :, :C], sat=sat)
-            ops.gemm_grouped_split(catp, lay.qkv_w, None, qkv, G, M, 3 * C, C, 2 * C, 3 * C, M * 2 * C, 3 * C * 2 * C, 0, M * 3 * C,
-                                   w_scale=wsc(lay.qkv_w), sat=sat)
-            ops.linattn_kv(qkv, kv, kvw, G, nimg, n, C)
-            ops.linattn_apply(qkv, kv, msg, C, G, nimg, n, C)
-            ops.split_planes(msg, msgp[0], msgp[1], sat=sat)
-            ops.gemm_grouped_split(msgp, lay.merge_w, None, mrg, G, M, C, C, C, C, M * C, C * 2 * C, 0, M * C, w_scale=wsc(lay.merge_w), sat=sat)
-            ops.layernorm(mrg, lay.n1w, lay.n1b, 1e-5, out=(catp[0][:, :, C:], catp[1][:, :, C:]), ldo=2 * C, rows_out=G * M,
-                          rows_per_img=G * M, wgroup_rows=M, sat=sat)
-            ops.gemm_grouped_split(catp, lay.mlp0_w, None, hidp, G, M, 2 * C, 2 * C, 2 * C, 2 * C, M * 2 * C, 2 * C * 2 * 2 * C, 0,
-                                   M * 2 * C, act=ops.ACT_RELU, w_scale=wsc(lay.mlp0_w), sat=sat)
-            ops.gemm_grouped_split(hidp, lay.mlp2_w, None, mrg, G, M, C, 2 * C, 2 * C, C, M * 2 * C, C * 2 * 2 * C, 0, M * C,
-                                   w_scale=wsc(lay.mlp2_w), sat=sat)
-        elif fused_att:
-            ops.linattn_kv_fused(cat, lay.qkv_w, kv, kvw, G, nimg, n, C)
-            ops.linattn_apply_fused(cat, lay.qkv_w, kv, cat[:, :, C:], G, nimg, n, C, merge_w=lay.merge_w, ln_w=lay.n1w, ln_b=lay.n1b)
-            ops.gemm_grouped(cat, lay.mlp0_w, None, hid, G, M, 2 * C, 2 * C, 2 * C, 2 * C, 2 * C, M * 2 * C, 4 * C * C, 0,
-                             M * 2 * C, act=ops.ACT_RELU)
-        else:
-            ops.gemm_grouped(cat, lay.qkv_w, None, qkv, G, M, 3 * C, C, 2 * C, C, 3 * C, M * 2 * C, 3 * C * C, 0, M * 3 * C)
-            ops.linattn_kv(qkv, kv, kvw, G, nimg, n, C)
-            ops.linattn_apply(qkv, kv, msg, C, G, nimg, n, C)
-            fused_ln = C == 128 and lp != torch.float32   # 16-bit operands: Linear(-> 128) + LayerNorm in one pass (mk_gemm_ln128)
-            if fused_ln:
-                ops.gemm_ln128(msg, lay.merge_w, lay.n1w, lay.n1b, 1e-5, cat[:, :, C:], G, M, C, ldo=2 * C)
-            else:
-                ops.gemm_grouped(msg, lay.merge_w, None, mrg, G, M, C, C, C, C, C, M * C, C * C, 0, M * C)
-                ops.layernorm(mrg, lay.n1w, lay.n1b, 1e-5, out=cat[:, :, C:], ldo=2 * C, rows_out=G * M, rows_per_img=G * M,
-                              wgroup_rows=M)
-            ops.gemm_grouped(cat, lay.mlp0_w, None, hid, G, M, 2 * C, 2 * C, 2 * C, 2 * C, 2 * C, M * 2 * C, 4 * C * C, 0,
-                             M * 2 * C, act=ops.ACT_RELU)
-            if not fused_ln:
-                ops.gemm_grouped(hid, lay.mlp2_w, None, mrg, G, M, C, 2 * C, 2 * C, 2 * C, C, M * 2 * C, 2 * C * C, 0, M * C)
-        if split:   # the layer's output as operand planes: of the next layer's `cat`, or (last) of resblock4's bordered input
-            o2 = (x4h, x4l) if last else (catp[0][:, :, :C], catp[1][:, :, :C])
-        else:
-            o2 = x4 if last else cat
-        if not split and C == 128 and lp != torch.float32:   # (fused_ln above): mlp[2] + norm2 + the layer's residual in one pass
-            ops.gemm_ln128(hid, lay.mlp2_w, lay.n2w, lay.n2b, 1e-5, o2, G, M, 2 * C, ldo=C if last else 2 * C, resid=xs,
-                           bordered=(nimg, gh, gw) if last else None)
-        else:
-            ops.layernorm(mrg, lay.n2w, lay.n2b, 1e-5, out=o2, ldo=C if last else 2 * C, resid=xs,
-                          rows_out=G * M, rows_per_img=G * M, wgroup_rows=M, bordered=(nimg, gh, gw) if last else None,
-                          sat=sat if split else None)
-    # ---- resblock4 ----
-    kpw, dw = W.rb4_kp, W.rb4_dsc
-    ck = kpw.cout
-    f4 = ws.get("rb4_f", (3, M, ck), torch.float32, dev)
-    cd = dw.cout
-    fd = ws.get("rb4_fd", (M, cd), torch.float32, dev)
-    if split:
-        h4p = plane_pair("rb4_h", (3, R, ck))
-        ops.conv3x3_split((x4h[:3], x4l[:3]), C, kpw.w1, kpw.b1, h4p, ck, 3, nimg, gh, gw, act=ops.ACT_RELU, stride_in1=R * C, w_scale=wsc(kpw.w1), sat=sat,
-                          stride_w=kpw.w1.shape[1] * kpw.w1.shape[2], stride_bias=ck, stride_out=R * ck, out_bordered=True)
-        assert kpw.has_sc and dw.has_sc   # (weights.prepare gives the descriptor block identity shortcut columns in this mode)
-        ops.conv3x3_split(h4p, ck, kpw.w2, kpw.b2, f4, ck, 3, nimg, gh, gw, act=ops.ACT_RELU, w_scale=wsc(kpw.w2),
-                          in2=(x4h[:3], x4l[:3]), C2=C, stride_in1=R * ck, stride_in2=R * C,
-                          stride_w=kpw.w2.shape[1] * kpw.w2.shape[2], stride_bias=ck, stride_out=M * ck)
-        hdp = plane_pair("rb4_hd", (R, cd))
-        ops.conv3x3_split((x4h[3], x4l[3]), C, dw.w1, dw.b1, hdp, cd, 1, nimg, gh, gw, act=ops.ACT_RELU, out_bordered=True, w_scale=wsc(dw.w1), sat=sat)
-        ops.conv3x3_split(hdp, cd, dw.w2, dw.b2, fd, cd, 1, nimg, gh, gw, act=ops.ACT_NONE, w_scale=wsc(dw.w2),
-                          in2=(x4h[3], x4l[3]), C2=C)   # relu=False, mickey_extractor.py:246
-    else:
-        h4 = ws.get("rb4_h" + geo, (3, R, ck), lp, dev, zero=True)
-        hd = ws.get("rb4_hd" + geo, (R, cd), lp, dev, zero=True)
-        ops.conv3x3(x4, C, kpw.w1, kpw.b1, h4, ck, 3, nimg, gh, gw, act=ops.ACT_RELU, stride_in1=R * C,
-                    stride_w=kpw.w1.shape[1] * kpw.w1.shape[2], stride_bias=ck, stride_out=R * ck, out_bordered=True)
-        ops.conv3x3(h4, ck, kpw.w2, kpw.b2, f4, ck, 3, nimg, gh, gw, act=ops.ACT_RELU,
-                    in2=x4 if kpw.has_sc else None, C2=C, resid=None if kpw.has_sc else x4, stride_in1=R * ck,
-                    stride_in2=R * C, stride_resid=R * C, stride_w=kpw.w2.shape[1] * kpw.w2.shape[2], stride_bias=ck,
-                    stride_out=M * ck)
-        ops.conv3x3(x4[3], C, dw.w1, dw.b1, hd, cd, 1, nimg, gh, gw, act=ops.ACT_RELU, out_bordered=True)
-        ops.conv3x3(hd, cd, dw.w2, dw.b2, fd, cd, 1, nimg, gh, gw, act=ops.ACT_NONE,   # relu=False, mickey_extractor.py:246
-                    in2=x4[3] if dw.has_sc else None, C2=C, resid=None if dw.has_sc else x4[3])
-    kh = mk["KP_HEADS"]
-    return ops.head_tails(f4[0], W.w_score, f4[1], W.w_xy, f4[2], W.w_depth, fd, nimg, gh, gw, ck, cd, border=3,
+    -> scr [nimg,1,n], kps [nimg,2,n] (absolute pixels), depth [nimg,1,n], dsc [nimg,Cd,n], all fp32.  Every activation a 3x3
+    conv reads is bordered; what only row-wise kernels read is dense.  The plane-writing kernels report saturation / NaN into
+    ws.sat_flag (per workspace = per model: no shared word)."""
+    grid = (nimg, gh, gw)
+    x = _conv_stack(W, ws, feat, grid)
+    xs, cat = _position_encoding(W, ws, x, grid, cfg)
+    x4 = _attention_layers(W, ws, xs, cat, grid, cfg)
+    f4, fd = _resblock4(W, ws, x4, grid)
+    mk, kh = cfg["MICKEY"], cfg["MICKEY"]["KP_HEADS"]
+    return ops.head_tails(f4[0], W.w_score, f4[1], W.w_xy, f4[2], W.w_depth, fd, nimg, gh, gw, f4.shape[-1], fd.shape[-1], border=3,
                           use_softmax=bool(kh["USE_SOFTMAX"]), use_depth_sigmoid=bool(kh["USE_DEPTHSIGMOID"]),
                           max_depth=float(kh["MAX_DEPTH"]), norm_dsc=bool(mk["DSC_HEAD"]["NORM_DSC"]),
                           down=float(mk["DINOV2"]["DOWN_FACTOR"]))

@@ -59,7 +59,7 @@ def prepare_encoder(sd, device, lp_dtype=torch.bfloat16, prefix=DINO_PREFIX, W=N
     """ln_fold: also prepare norm1 / norm2 folded into qkv / fc1 (16-bit operand types only): the encoder then runs without
     stand-alone LayerNorm passes (pipeline.encoder_forward)."""
     W = DeviceWeights() if W is None else W
-    W.lp = lp_dtype
+    W.lp, W.lp_heads, W.heads_split, W.features_lp = lp_dtype, lp_dtype, False, False   # (an encoder alone: prepare sets the heads' own)
     dev = device
 
     def lp(t):
@@ -161,7 +161,7 @@ def prepare(sd, cfg, device, lp_dtype=torch.bfloat16, heads_dtype=None, ln_fold=
             sc = split_weight_scale(t)
             out = split_conv_weight(t, sc).to(device=dev).contiguous()
             out.mk_scale = sc   # the power-of-two scale of its planes travels WITH the tensor object (a copy / .to() of it has
-            #                     no such attribute: pipeline.wsc raises instead of reading a stale scale by address)
+            #                     no such attribute: pipeline._wscale raises instead of reading a stale scale by address)
             return out
         return t.to(device=dev, dtype=W.lp_heads).contiguous()
 
