@@ -462,6 +462,47 @@ int mk_train_desc_l2norm_fwd(const float* x, float* y, float* rnorm, int nimg, i
 int mk_train_desc_l2norm_bwd(const float* g, const float* y, const float* rnorm, float* gx, int nimg, int n, int C,
                              mk_stream_t stream);
 
+/* The glue of the heads' BasicBlock for TRAINING (utils/extractor_utils.py:12-35 under autograd; 16 blocks per model,
+ * mickey_extractor.py:76-79,155-158,194-197,232-235): nn.BatchNorm2d (extractor_utils.py:19,21) with the residual add (:32) and
+ * F.relu (:30,33-34) in the same pass, forward and backward.  The bias-free 1x1 shortcut (:23-26,29) is mk_train_linear_* above.
+ * fp32 data, vector ALU only; the forward computes in fp32, the backward's per-channel sums and x - mean terms in fp64 (below).
+ * Rows are [M, C], channels innermost (channels_last memory, M = B H W), C a multiple of 4 in [4, 1024], row
+ * strides (elements) multiples of 4 and >= C, every pointer 16-byte aligned.  Every per-channel sum runs over chunks of
+ * mk_train_bn_chunk_rows() rows (mk_train_bn_chunks(M) of them, a function of M alone): 16 row slots in slot order, then the chunks
+ * in chunk order (four consecutive runs, then the four sums in order).  No atomics, no host sync, bit-identical from run to run; a
+ * launch writes the chunk partials into work (mk_train_bn_work_floats(M, C) floats: the backward's four rows of C doubles per chunk, of which the forward uses two rows of floats) and the next launch combines them in its
+ * prologue, every workgroup for its own 64 channels.
+ *
+ * mk_train_bn_fwd: y = act(xhat gamma + beta (+ resid)), xhat = (x - mean) rstd, rstd = 1 / sqrt(var + eps), act = max(., 0) with
+ *   relu != 0 (a NaN stays a NaN), resid NULL: none.
+ *   training != 0 (2 launches; M > 1): mean and the biased var of the batch.  Launch 1 leaves per chunk its mean (taken as K + sum(x - K)
+ *   / n, K the chunk's first row) and its sum of squares about that mean; launch 2 combines them as centred moments,
+ *   mean = m_0 + sum_k n_k (m_k - m_0) / M, var = sum_k (M2_k + n_k (m_k - mean)^2) / M: a channel mean 1000 times its spread costs no
+ *   digits.  The workgroups of chunk 0 then write running_mean = (1 - momentum) running_mean + momentum mean, running_var likewise
+ *   with var M / (M - 1), and num_batches_tracked += 1 (the module's int64 buffer where it lies in device memory).
+ *   training == 0 (1 launch): mean = running_mean, var = running_var; nothing is updated, work may be NULL.
+ *   mean [C], rstd [C]: what the backward needs (either may be NULL: not kept).  mask [M, C] bytes, dense: 1 where y > 0 (relu only;
+ *   NULL: not kept).  A NaN or Inf in x reaches every output of its channel in training, its own element in eval.
+ * mk_train_bn_bwd (2 launches): g' = g where mask != 0, else 0 (mask NULL: g' = g; no ReLU).  xhat is recomputed from x, mean, rstd.
+ *   Launch 1 leaves per chunk sum g', sum g' (x - mean), sum (x - mean)^2 and sum (x - mean), taken in double.  In training the
+ *   variance is retaken from them about mean + delta, delta = mean(x - mean) being the rounding the fp32 mean carries, and launch 2
+ *   forms x - mean - delta in double too, so that g' (1 - xhat^2), all that is left of gx when a channel has a handful of rows, keeps
+ *   its digits (eps: the forward's).  Launch 2 combines the partials and writes
+ *   gx = gamma rstd (g' - mean(g') - xhat mean(g' xhat))   (training == 0: gamma rstd g'),   gresid = g',
+ *   and from the workgroups of chunk 0 dgamma = sum g' xhat, dbeta = sum g'.  gx, gresid, dgamma, dbeta: NULL = not wanted (without
+ *   gx and gresid launch 2 is one chunk tall; with none of the four nothing is launched).  Gradients are bit-linear in g under a
+ *   power-of-two scale; a NaN in g reaches every gradient of its channel in training. */
+int mk_train_bn_chunk_rows(void);
+int mk_train_bn_chunks(long long M);
+long long mk_train_bn_work_floats(long long M, int C);
+int mk_train_bn_fwd(const float* x, long long ldx, const float* gamma, const float* beta, const float* resid, long long ldr,
+                    float* running_mean, float* running_var, long long* num_batches_tracked, float momentum, float eps, float* work,
+                    float* y, long long ldy, float* mean, float* rstd, unsigned char* mask, int M, int C, int relu, int training,
+                    mk_stream_t stream);
+int mk_train_bn_bwd(const float* g, long long ldg, const float* x, long long ldx, const float* gamma, const float* mean,
+                    const float* rstd, const unsigned char* mask, float* work, float* gx, long long ldgx, float* gresid,
+                    long long ldgr, float* dgamma, float* dbeta, float eps, int M, int C, int training, mk_stream_t stream);
+
 /* Head tails (mickey_extractor.py:134-138,173-176,213-216,246-249 and
  * compute_correspondences.py:20-31).  feat* fp32 [nimg*h*w, C] (resblock4 outputs).
  *   scr   [nimg, h*w]      border-masked temperature-100 softmax (or sigmoid) of w_score . feat_det

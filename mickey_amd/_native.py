@@ -78,6 +78,11 @@ SIGNATURES = {
     "mk_train_headtail_bwd": ("i", "ppppppppiiiiiffp"),
     "mk_train_desc_l2norm_fwd": ("i", "pppiiifp"),
     "mk_train_desc_l2norm_bwd": ("i", "ppppiiip"),
+    "mk_train_bn_chunk_rows": ("i", ""),
+    "mk_train_bn_chunks": ("i", "l"),
+    "mk_train_bn_work_floats": ("l", "li"),
+    "mk_train_bn_fwd": ("i", "plppplpppffpplpppiiiip"),
+    "mk_train_bn_bwd": ("i", "plplpppppplplppfiiip"),
     "mk_head_tails": ("i", "pppppppppppiiiiiiiififp"),
     "mk_dual_softmax_work_floats": ("l", "iiii"),
     "mk_dual_softmax": ("i", "ppppfifppppiiiip"),

@@ -660,6 +660,72 @@ def train_desc_l2norm_bwd(g, y, rnorm, nimg, n, C, out=None):
     return out
 
 
+# ---- training: BatchNorm + residual + ReLU of the heads' BasicBlock (mickey_hip.h: mk_train_bn_*; train_block.py).  Operands are 2-D
+# fp32 [M, C] device tensors with dense, 16-byte aligned rows (any row stride that is a multiple of 4); outputs may be passed in. ------
+BN_CHUNK_ROWS = 256   # rows of one statistics partial == mk_train_bn_chunk_rows() (tests/test_train_block_cpu.py)
+BN_MIN_C, BN_MAX_C = 4, 1024
+
+
+def bn_chunks(M):
+    """chunks of the per-channel sums over M rows: a function of M alone."""
+    return -(-M // BN_CHUNK_ROWS) if M > 0 else 0   # == mk_train_bn_chunks(M), without the call
+
+
+def _vec(t, C):
+    assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == C and t.data_ptr() % 16 == 0
+    return ptr(t)
+
+
+def train_bn_fwd(x, gamma, beta, running_mean, running_var, num_batches_tracked, training, momentum, eps, resid=None, relu=True,
+                 want_saved=True, out=None, stats=None, mask=None, work=None):
+    """mk_train_bn_fwd: x [M, C] -> (y [M, C], stats [2, C] = mean | rstd or None, mask uint8 [M, C] or None); 2 launches in training
+    (which also updates the running statistics), 1 in eval.  stats and mask are None unless want_saved (mask: and relu)."""
+    M, C = x.shape
+    dev = x.device
+    if out is None:
+        out = torch.empty((M, C), device=dev, dtype=torch.float32)
+    if want_saved:
+        if stats is None:
+            stats = torch.empty((2, C), device=dev, dtype=torch.float32)
+        if relu and mask is None:
+            mask = torch.empty((M, C), device=dev, dtype=torch.uint8)
+        assert stats.is_contiguous() and stats.numel() == 2 * C and (mask is None or (mask.is_contiguous() and mask.numel() == M * C))
+    else:
+        stats = mask = None
+    if training and work is None:
+        work = torch.empty((bn_chunks(M) * 2 * C,), device=dev, dtype=torch.float32)
+    assert not training or (work.is_contiguous() and work.numel() >= bn_chunks(M) * 2 * C)
+    assert num_batches_tracked is None or (num_batches_tracked.dtype == torch.int64 and num_batches_tracked.numel() == 1)
+    call("mk_train_bn_fwd", *_mat(x), _vec(gamma, C), _vec(beta, C), *_mat(resid), _vec(running_mean, C), _vec(running_var, C),
+         ptr(num_batches_tracked), float(momentum), float(eps), ptr(work) if training else None, *_mat(out),
+         ptr(stats) if want_saved else None, ptr(stats[1]) if want_saved else None, ptr(mask), M, C, int(bool(relu)), int(bool(training)),
+         stream())
+    return out, stats, mask
+
+
+def train_bn_bwd(g, x, gamma, stats, mask, training, eps, want_gx=True, want_gresid=False, want_affine=True, gx=None, gresid=None,
+                 affine=None, work=None):
+    """mk_train_bn_bwd: g, x [M, C], stats [2, C], mask uint8 [M, C] or None (no ReLU) -> (gx [M, C] or None, gresid [M, C] or None,
+    affine [2, C] = dgamma | dbeta or None); 2 launches, none when nothing is wanted."""
+    M, C = x.shape
+    dev = g.device
+    assert g.shape == x.shape and stats.is_contiguous() and stats.numel() == 2 * C and stats.data_ptr() % 16 == 0
+    assert mask is None or (mask.dtype == torch.uint8 and mask.is_contiguous() and mask.numel() == M * C)
+    if want_gx and gx is None:
+        gx = torch.empty((M, C), device=dev, dtype=torch.float32)
+    if want_gresid and gresid is None:
+        gresid = torch.empty((M, C), device=dev, dtype=torch.float32)
+    if want_affine and affine is None:
+        affine = torch.empty((2, C), device=dev, dtype=torch.float32)
+    if work is None:
+        work = torch.empty((bn_chunks(M) * 8 * C,), device=dev, dtype=torch.float32)
+    assert work.is_contiguous() and work.numel() >= bn_chunks(M) * 8 * C and work.data_ptr() % 16 == 0
+    call("mk_train_bn_bwd", *_mat(g), *_mat(x), _vec(gamma, C), ptr(stats), ptr(stats[1]), ptr(mask), ptr(work),
+         *_mat(gx if want_gx else None), *_mat(gresid if want_gresid else None), ptr(affine) if want_affine else None,
+         ptr(affine[1]) if want_affine else None, float(eps), M, C, int(bool(training)), stream())
+    return (gx if want_gx else None), (gresid if want_gresid else None), (affine if want_affine else None)
+
+
 def head_tails(f_det, w_score, f_off, w_xy, f_dep, w_dep, f_dsc, nimg, h, w, C, Cd, border=3, use_softmax=True,
                use_depth_sigmoid=False, max_depth=60.0, norm_dsc=True, down=14.0):
     dev = f_det.device

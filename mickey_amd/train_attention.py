@@ -24,7 +24,7 @@ value computed from it.
                                             use_hip_encoder / use_hip_convs)
 
 Not covered here: the q / k / v / merge / MLP nn.Linears and the LayerNorms of EncoderLayer (train_layer.py runs the whole layer
-around this core as one node); BatchNorm, ReLU and the 1x1 convolutions (they stay in torch); autocast and half-precision inputs (ValueError); double backward; head sizes other than 16; hipGraph capture
+around this core as one node); BatchNorm, ReLU and the 1x1 shortcut of BasicBlock (train_block.py), the 1x1 tail convolutions (train_tails.py); autocast and half-precision inputs (ValueError); double backward; head sizes other than 16; hipGraph capture
 of a step.
 """
 import torch

@@ -18,8 +18,8 @@ every value computed from it NaN, so the trainer's finite check (model.py:139-14
     Conv3x3(cin, cout)           nn.Module with nn.Conv2d's `weight` Parameter and state-dict key
     use_hip_convs(model)         swaps it into a reference-style model in place (next to use_hip_matcher / use_hip_encoder)
 
-BatchNorm (batch statistics in training), ReLU, the 1x1 shortcut / score / offset / depth convolutions and the attention layers
-stay in torch.  Autocast is not covered: inputs and weights must be float32 (a half-precision input raises ValueError).
+BatchNorm (batch statistics in training), ReLU and the 1x1 shortcut are train_block.py, the 1x1 score / offset / depth convolutions
+train_tails.py, the attention layers train_layer.py.  Autocast is not covered: inputs and weights must be float32 (a half-precision input raises ValueError).
 """
 import torch
 import torch.nn.functional as F

@@ -23,7 +23,7 @@ rows x 128 x 4 bytes, plus two [rows] rstd vectors and the attention's [N 8, 272
     encoder_layer_formula(...)                  the same layer in plain torch, any device / dtype (tests, documentation)
 
 Not covered: d_model other than 128 or nhead other than 8 (ValueError), biases, autocast and half precision (ValueError), double
-backward, hipGraph capture of a step, BatchNorm / ReLU / the 1x1 convolutions of BasicBlock, the head tails (train_tails.py), the positional
+backward, hipGraph capture of a step, BatchNorm / ReLU / the 1x1 shortcut of BasicBlock (train_block.py), the head tails (train_tails.py), the positional
 encoding and the NCHW <-> token rearrangement around the stack.
 """
 import torch

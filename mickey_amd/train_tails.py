@@ -18,8 +18,8 @@ descriptors come out contiguous [B, C, H, W], the layout the matcher reads.
     use_hip_tails(model)                                                     swaps them into a reference-style model, returns the count
 
 Not covered: 1x1 convs with a bias or more than 2 outputs, widths that are no multiple of 4 or beyond 256 (ValueError), autocast and
-half precision (ValueError), double backward, hipGraph capture of a step, BatchNorm / ReLU / the shortcut of BasicBlock, the
-positional encoding, get_abs_kpts_coordinates, one launch across the four heads.
+half precision (ValueError), double backward, hipGraph capture of a step, BatchNorm / ReLU / the shortcut of BasicBlock (they are
+train_block.py), the positional encoding, get_abs_kpts_coordinates, one launch across the four heads.
 """
 import inspect
 import numbers
