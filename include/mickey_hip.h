@@ -503,6 +503,49 @@ int mk_train_bn_bwd(const float* g, long long ldg, const float* x, long long ldx
                     const float* rstd, const unsigned char* mask, float* work, float* gx, long long ldgx, float* gresid,
                     long long ldgr, float* dgamma, float* dbeta, float eps, int M, int C, int training, mk_stream_t stream);
 
+/* The tail of a training step (lib/models/MicKey/model.py:104-145): the isnan / isinf checks of :104-108 and :140 (six host
+ * synchronisations there), torch.nn.utils.clip_grad_norm_ (:137) and torch.optim.Adam.step (:145; created at :284 with eps = 1e-6), as three
+ * launches without a host synchronisation.  fp32 tensors, vector ALU only; the sums of squares and the bias corrections in fp64.
+ *
+ * The kernels follow a TABLE in device memory, one mk_optim_row per tensor, and a CHUNK MAP next to it: the tensors are cut into
+ * chunks of mk_optim_chunk_elems() elements (mk_optim_chunks(numel) per tensor, a function of numel alone; a chunk never spans two
+ * tensors), and entry c of the map is two ints, the row of chunk c and its index inside that tensor.  One workgroup runs one chunk.
+ * The library cannot look into the table: the caller vouches that every pointer of a row addresses numel fp32 elements (any memory
+ * order: the ops are element-wise, the four tensors of a row share one order) and that the map's entries lie inside the table.  An
+ * entry that names no row, or a chunk past its tensor's end, is skipped.  A tensor is read and written with 16-byte accesses when
+ * every pointer the kernel follows for it is 16-byte aligned, with dword accesses otherwise; results do not depend on which.
+ *   p, m, v   parameter, exp_avg, exp_avg_sq (MK_OPTIM_PARAM rows; NULL on a row that is only checked)
+ *   g         the gradient, or a tensor that is only checked for NaN / Inf
+ *   step      mk_optim_chunks(numel) fp32 cells that all hold the tensor's step count: the workgroup of chunk i reads and writes
+ *             cell i alone, so that no workgroup reads a cell that another one writes in the same launch
+ *   flags     MK_OPTIM_NORM: g counts towards the norm; MK_OPTIM_PARAM: the row takes the Adam update
+ *
+ * mk_optim_grad_stats: partials[c] (2 chunks doubles, 16-byte aligned) = { s, s on a MK_OPTIM_NORM row else 0 }, s = the sum of g^2
+ *   over chunk c in double, lanes in a fixed order.  An fp32 square cannot overflow a double: s is non-finite exactly when the
+ *   chunk holds a NaN or an Inf.
+ * mk_optim_reduce (one workgroup): adds both columns in chunk order and writes state[4] = { ok, total_norm, clip_coef, 0 }:
+ *   ok = 1 when every partial is finite, else 0; total_norm = sqrt(sum over the MK_OPTIM_NORM rows), rounded once to fp32;
+ *   clip_coef = min(1, max_norm / (total_norm + 1e-6)) in fp32 as clip_grad_norm_ computes it, 1 with max_norm < 0 (no clipping).
+ * mk_optim_adam: over the first `chunks` entries of the map (the caller puts the MK_OPTIM_PARAM rows first).  state[0] == 0: returns
+ *   without touching anything.  Else g' = g clip_coef (stored back to g only when clip_coef < 1), g' += weight_decay p when
+ *   weight_decay != 0, and with t = step + 1:  m = beta1 m + (1 - beta1) g',  v = beta2 v + (1 - beta2) g'^2,
+ *   p -= (lr / (1 - beta1^t)) m / (sqrt(v) / sqrt(1 - beta2^t) + eps);  step = t.  The scalars in double once per workgroup, the
+ *   element math in fp32.  Plain Adam is this launch alone with state = { 1, -, 1, - }.
+ * No atomics; bit-identical from run to run. */
+typedef struct mk_optim_row {
+  float *p, *g, *m, *v, *step;
+  long long numel;
+  double lr, beta1, beta2, eps, weight_decay;
+  long long flags;
+} mk_optim_row; /* 96 bytes */
+#define MK_OPTIM_NORM 1
+#define MK_OPTIM_PARAM 2
+int mk_optim_chunk_elems(void);
+long long mk_optim_chunks(long long numel);
+int mk_optim_grad_stats(const mk_optim_row* table, int rows, const int* chunk_map, int chunks, double* partials, mk_stream_t stream);
+int mk_optim_reduce(const double* partials, int chunks, float max_norm, float* state, mk_stream_t stream);
+int mk_optim_adam(const mk_optim_row* table, int rows, const int* chunk_map, int chunks, const float* state, mk_stream_t stream);
+
 /* Head tails (mickey_extractor.py:134-138,173-176,213-216,246-249 and
  * compute_correspondences.py:20-31).  feat* fp32 [nimg*h*w, C] (resblock4 outputs).
  *   scr   [nimg, h*w]      border-masked temperature-100 softmax (or sigmoid) of w_score . feat_det

@@ -83,6 +83,11 @@ SIGNATURES = {
     "mk_train_bn_work_floats": ("l", "li"),
     "mk_train_bn_fwd": ("i", "plppplpppffpplpppiiiip"),
     "mk_train_bn_bwd": ("i", "plplpppppplplppfiiip"),
+    "mk_optim_chunk_elems": ("i", ""),
+    "mk_optim_chunks": ("l", "l"),
+    "mk_optim_grad_stats": ("i", "pipipp"),
+    "mk_optim_reduce": ("i", "pifpp"),
+    "mk_optim_adam": ("i", "pipipp"),
     "mk_head_tails": ("i", "pppppppppppiiiiiiiififp"),
     "mk_dual_softmax_work_floats": ("l", "iiii"),
     "mk_dual_softmax": ("i", "ppppfifppppiiiip"),
