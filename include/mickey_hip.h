@@ -616,6 +616,51 @@ int mk_sinkhorn_kf(const float* dsc0, const float* dsc1, const float* scr0, cons
                    float* scores, float* kp_scores, float* final_scores, float* work, int B, int C, int n0, int n1,
                    const int* kf_index, int K, mk_stream_t stream);
 
+/* Pair-list mode of the three matchers: B pairs drawn from image sets that are encoded once -- a map on EACH operand (a sequence:
+ * pairs (i, i+1) of N frames; Q queries against K keyframes; all pairs of a small collection).  No counterpart in the reference,
+ * whose matcher takes one image-0 and one image-1 row per pair (compute_correspondences.py:52-92 builds both per pair,
+ * feature_matcher.py:64-83 / :93-137 consume them; lib/datasets/mapfree.py:83-99 lists a frame once per pair it appears in): the
+ * results are those of the entry point without a suffix on the materialised operands dsc0[idx0], dsc1[idx1], ..., bit for bit.
+ * Arguments as that entry point, plus, in front of the stream:
+ *   idx0, idx1  int32 [B] device maps: pair b reads row idx0[b] of operand 0 (dsc0 [N0, C, n0], scr0 [N0, n0]) and row idx1[b] of
+ *               operand 1 (dsc1 [N1, C, n1], scr1 [N1, n1]).  NULL = the identity on that side; its row count must then equal B.
+ *               Both NULL: the call IS the plain one.  idx1 == NULL: the call IS the _kf one (which is implemented on top of this).
+ *   N0, N1      rows of operand 0 / 1; NOT limited by B (the K <= B of keyframe mode is a rule of that mode's callers only).
+ *   dsc0 == dsc1 (with scr0 == scr1) is the usual case: one image set, both maps into it.
+ *   PRECONDITION: 0 <= idx0[b] < N0 and 0 <= idx1[b] < N1; the caller validates on the host (mickey_amd.ops.check_pair_index).  A
+ *               kernel never dereferences an entry outside its operand's rows: the workgroups of such a pair return before their
+ *               first load and its outputs are left unwritten.
+ * Everything that belongs to a pair (outputs, partials, log-sums) is indexed by the pair.
+ * Work sizes: mk_dual_softmax_pairs: mk_dual_softmax_work_floats(B, n0, n1, own_copy); mk_sinkhorn_pairs:
+ * mk_sinkhorn_work_floats(B, n0, n1) -- both hold per-pair data only.  mk_dual_softmax_split_pairs:
+ * mk_dual_softmax_split_pairs_work_floats(B, n0, n1, N0, N1, shared) = the split planes of N0 + N1 images (shared != 0: of the N0
+ * images of ONE set, which is what the call makes when dsc0 == dsc1, n0 == n1 and N0 == N1) + the per-pair part. */
+int mk_dual_softmax_pairs(const float* dsc0, const float* dsc1, const float* scr0, const float* scr1, float inv_temperature,
+                          int use_dustbin, float dustbin, float* scores, float* kp_scores, float* final_scores, float* work, int B,
+                          int C, int n0, int n1, const int* idx0, const int* idx1, int N0, int N1, mk_stream_t stream);
+long long mk_dual_softmax_split_pairs_work_floats(int B, int n0, int n1, int N0, int N1, int shared);
+int mk_dual_softmax_split_pairs(const float* dsc0, const float* dsc1, const float* scr0, const float* scr1, float inv_temperature,
+                                int use_dustbin, float dustbin, float* scores, float* kp_scores, float* final_scores, float* work,
+                                int B, int C, int n0, int n1, const int* idx0, const int* idx1, int N0, int N1, mk_stream_t stream);
+int mk_sinkhorn_pairs(const float* dsc0, const float* dsc1, const float* scr0, const float* scr1, float alpha, int iters,
+                      float* scores, float* kp_scores, float* final_scores, float* work, int B, int C, int n0, int n1,
+                      const int* idx0, const int* idx1, int N0, int N1, mk_stream_t stream);
+
+/* The two halves of mk_dual_softmax_split_pairs for a caller that walks a long pair list in chunks (same reference lines): the
+ * split planes of an image set are made ONCE, then every chunk of pairs runs the two correlation passes on them.
+ * mk_dsc_split_planes: dsc fp32 [N, C = 128, n] -> planes, mk_dsc_split_planes_floats(N, n) fp32 elements, 16-byte aligned (the
+ *   plane layout is the same for both sides: one set serves as operand 0 and as operand 1).
+ * mk_dual_softmax_split_planes: mk_dual_softmax_split_pairs with planes0 / planes1 (of N0 / N1 images, may be the same buffer) in
+ *   place of dsc0 / dsc1 and C; work: mk_dual_softmax_split_planes_work_floats(B, n0, n1) fp32 elements (per-pair data only),
+ *   16-byte aligned.  Same bits as mk_dual_softmax_split_pairs. */
+long long mk_dsc_split_planes_floats(int N, int n);
+int mk_dsc_split_planes(const float* dsc, float* planes, int N, int C, int n, mk_stream_t stream);
+long long mk_dual_softmax_split_planes_work_floats(int B, int n0, int n1);
+int mk_dual_softmax_split_planes(const float* planes0, const float* planes1, const float* scr0, const float* scr1,
+                                 float inv_temperature, int use_dustbin, float dustbin, float* scores, float* kp_scores,
+                                 float* final_scores, float* work, int B, int n0, int n1, const int* idx0, const int* idx1, int N0,
+                                 int N1, mk_stream_t stream);
+
 /* Training: the dual softmax with its backward (reference lib/models/MicKey/model.py:124-134 back-propagates d loss / d final_scores
  * through final_scores = dualSoftmax(dsc0, dsc1) * kp_matrix_scores: feature_matcher.py:64-83, compute_correspondences.py:46-50,
  * model.py:201).  C == 128; split != 0 selects the split-fp16 correlation (preconditions of mk_dual_softmax_split), else exact fp32.
@@ -706,6 +751,15 @@ int mk_gather_backproject_kf(const int* idx, const float* final_scores, const fl
                              const float* kps1, const float* depth1, const float* K0, const float* K1, float* X, float* Y,
                              float* wts, float* corr, int B, int rows_per_pair, int k, int n0, int n1, const int* kf_index,
                              int K, mk_stream_t stream);
+
+/* Pair-list mode of mk_gather_backproject (probabilisticProcrustes.py:233-244 gathers kps0[b] / kps1[b] of per-pair tensors; here
+ * both come from image sets): kps0 [N0, 2, n0], depth0 [N0, n0] read through idx0 and kps1 [N1, 2, n1], depth1 [N1, n1] through
+ * idx1; K0 / K1 [B, 3, 3], idx, final_scores and the outputs stay per pair.  idx0, idx1, N0, N1, PRECONDITION and out-of-range
+ * behaviour as mk_dual_softmax_pairs. */
+int mk_gather_backproject_pairs(const int* idx, const float* final_scores, const float* kps0, const float* depth0,
+                                const float* kps1, const float* depth1, const float* K0, const float* K1, float* X, float* Y,
+                                float* wts, float* corr, int B, int rows_per_pair, int k, int n0, int n1, const int* idx0,
+                                const int* idx1, int N0, int N1, mk_stream_t stream);
 
 /* Backward of mk_gather_backproject w.r.t. keypoints and depths (training: loss_class.py:139-146 + training_utils.py:7-22 under
  * autograd; intrinsics and scores get no gradient).  gX, gY [B*rows_per_pair, k, 3] = dL/dX, dL/dY; corr as written by the forward;

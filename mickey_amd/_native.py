@@ -98,6 +98,14 @@ SIGNATURES = {
     "mk_dual_softmax_kf": ("i", "ppppfifppppiiiipip"),
     "mk_dual_softmax_split_kf": ("i", "ppppfifppppiiiipip"),
     "mk_sinkhorn_kf": ("i", "ppppfippppiiiipip"),
+    "mk_dual_softmax_pairs": ("i", "ppppfifppppiiiippiip"),
+    "mk_dual_softmax_split_pairs_work_floats": ("l", "iiiiii"),
+    "mk_dual_softmax_split_pairs": ("i", "ppppfifppppiiiippiip"),
+    "mk_sinkhorn_pairs": ("i", "ppppfippppiiiippiip"),
+    "mk_dsc_split_planes_floats": ("l", "ii"),
+    "mk_dsc_split_planes": ("i", "ppiiip"),
+    "mk_dual_softmax_split_planes_work_floats": ("l", "iii"),
+    "mk_dual_softmax_split_planes": ("i", "ppppfifppppiiippiip"),
     "mk_mutual_nn": ("i", "ppppiiip"),
     "mk_dual_softmax_train_work_floats": ("l", "iiii"),
     "mk_dual_softmax_train": ("i", "ppppfppppppiiiiip"),
@@ -109,6 +117,7 @@ SIGNATURES = {
     "mk_counter_add": ("i", "pup"),
     "mk_gather_backproject": ("i", "ppppppppppppiiiiip"),
     "mk_gather_backproject_kf": ("i", "ppppppppppppiiiiipip"),
+    "mk_gather_backproject_pairs": ("i", "ppppppppppppiiiiippiip"),
     "mk_gather_backproject_bwd": ("i", "ppppppppppiiiiip"),
     "mk_ransac_hypotheses": ("i", "pppppuupfppppiiilp"),
     "mk_refine_pose": ("i", "pppppfiipppppppiiiip"),

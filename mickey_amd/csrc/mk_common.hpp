@@ -51,6 +51,39 @@ __device__ __forceinline__ bool kf_row(const int* __restrict__ map, int K, int b
   return (unsigned)row < (unsigned)K;
 }
 
+// The row of each operand that pair b reads (mickey_hip.h: the *_kf and *_pairs entry points).  MAP_NONE: both b, compiles to
+// nothing.  MAP_KF: operand 0 through idx0 (kf_row<true>, unchanged), operand 1 is b.  MAP_PAIRS (pair-list mode): operand 0
+// through idx0 into N0 rows and operand 1 through idx1 into N1 rows, a NULL map being the identity on its side (its row count is
+// then the pair count, mickey_hip.h).  Block-uniform like kf_row; false for an entry outside its operand's rows: the workgroup
+// returns before its first load.
+constexpr int MAP_NONE = 0, MAP_KF = 1, MAP_PAIRS = 2;
+template <int MAP>
+__device__ __forceinline__ bool pair_rows(const int* __restrict__ idx0, int N0, const int* __restrict__ idx1, int N1, int b,
+                                          int& row0, int& row1) {
+  if (MAP != MAP_PAIRS) {
+    row1 = b;
+    return kf_row<MAP == MAP_KF>(idx0, N0, b, row0);
+  }
+  row0 = idx0 ? __builtin_amdgcn_readfirstlane(idx0[b]) : b;
+  row1 = idx1 ? __builtin_amdgcn_readfirstlane(idx1[b]) : b;
+  return (unsigned)row0 < (unsigned)N0 && (unsigned)row1 < (unsigned)N1;
+}
+
+// host side: the maps of one call and the instantiation they select (no map at all, operand 0 only = keyframe mode, else the
+// general one); check_row_maps is the *_pairs entry points' argument check, made before any launch
+struct RowMaps {
+  const int* idx0;
+  int N0;
+  const int* idx1;
+  int N1;
+  int mode() const { return idx1 ? MAP_PAIRS : idx0 ? MAP_KF : MAP_NONE; }
+};
+inline int check_row_maps(const char* who, const RowMaps& m, int B) {
+  MK_CHECK_ARG(m.idx0 ? m.N0 > 0 : m.N0 == B, "%s: need N0 > 0 with a map on operand 0, N0 == B without", who);
+  MK_CHECK_ARG(m.idx1 ? m.N1 > 0 : m.N1 == B, "%s: need N1 > 0 with a map on operand 1, N1 == B without", who);
+  return MK_OK;
+}
+
 // Split-operand planes (x * scale = hi + lo in fp16) saturate at fp16's largest finite value; a NaN stays a NaN (both planes), so
 // that a non-finite head activation reaches the outputs and the callers' finite checks.  flag: the per-call watcher word of the
 // plane-writing entry points (mickey_hip.h: sat_flag; null = nobody watches: no per-element work) gets bit 0 set by any kernel

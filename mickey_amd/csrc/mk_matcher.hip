@@ -56,17 +56,19 @@ __device__ __forceinline__ f32x16 corr_tile(const float* sA, const float* sB, in
 //     correlation (the fp32 matrix pipe is the bound of this stage: 64 MFMAs x 64 cycles per 32 x 32 tile).
 // amdgpu_waves_per_eu(2, 2): without it the scheduler chases occupancy, keeps ONE operand register and emits
 // load -> s_waitcnt vmcnt(0) -> MFMA 64 times per tile (64 serial memory round trips, measured 32 us per tile)
-// KF (keyframe mode): dsc0 holds K keyframes, pair b reads row kf[b] (kf_row); partials and vbuf stay per pair
-template <bool FULLC, bool KF>
+// MAP (mk_common.hpp: pair_rows): pair b reads row b0 of dsc0 and row b1 of dsc1 -- keyframe mode: dsc0 holds N0 keyframes, b0 =
+// idx0[b]; pair-list mode: a map on each side; partials and vbuf stay per pair
+template <bool FULLC, int MAP>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void lse_partial_kernel(const float* __restrict__ dsc0, const float* __restrict__ dsc1,
                                                           float scale2, float* __restrict__ partr, float* __restrict__ partc,
                                                           float* __restrict__ vbuf, int C, int n0, int n1, int nrb, int gx,
-                                                          int nunits, const int* __restrict__ kf, int K) {
-  int bx, by, b, b0;
+                                                          int nunits, const int* __restrict__ idx0, int N0,
+                                                          const int* __restrict__ idx1, int N1) {
+  int bx, by, b, b0, b1;
   if (!decode_unit_grid(gx, NCHUNK, nunits, bx, by, b)) return;
-  if (!kf_row<KF>(kf, K, b, b0)) return;
+  if (!pair_rows<MAP>(idx0, N0, idx1, N1, b, b0, b1)) return;
   const float* dA = dsc0 + (long long)b0 * C * n0;
-  const float* dB = dsc1 + (long long)b * C * n1;
+  const float* dB = dsc1 + (long long)b1 * C * n1;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int l31 = lane & 31, hi = lane >> 5;
   const int rb = bx * 4 + wave, i0 = rb * RT;
@@ -165,15 +167,16 @@ __global__ __launch_bounds__(256) void lse_final_kernel(const float* __restrict_
 
 // pass 2, element-wise.  grid (column blocks of 256*VEC, n0, B): scores = softmax_rows * softmax_cols =
 // 2^((v2 - lc2) + (v2 - lr2)), kp = scr0 (x) scr1, final = scores * kp.  `scores` or `fin` may alias vbuf (in place).
-// KF: scr0 holds K keyframes, pair b reads row kf[b]
-template <int VEC, bool KF>
+// MAP: pair b reads row b0 of scr0 and row b1 of scr1 (pair_rows)
+template <int VEC, int MAP>
 __global__ __launch_bounds__(256) void dual_softmax_apply_kernel(const float* vbuf, const float* __restrict__ scr0,
                                                                  const float* __restrict__ scr1, const float* __restrict__ lse2,
                                                                  float* scores, float* __restrict__ kp, float* fin, int n0, int n1,
-                                                                 int nmax, const int* __restrict__ kf, int K) {
+                                                                 int nmax, const int* __restrict__ idx0, int N0,
+                                                                 const int* __restrict__ idx1, int N1) {
   const int i = blockIdx.y, b = blockIdx.z;
-  int b0;
-  if (!kf_row<KF>(kf, K, b, b0)) return;
+  int b0, b1;
+  if (!pair_rows<MAP>(idx0, N0, idx1, N1, b, b0, b1)) return;
   const int j = (blockIdx.x * 256 + threadIdx.x) * VEC;
   if (j >= n1) return;
   const float lr = lse2[((long long)b * 2 + 0) * nmax + i];
@@ -183,7 +186,7 @@ __global__ __launch_bounds__(256) void dual_softmax_apply_kernel(const float* vb
   const VT v = __builtin_nontemporal_load((const VT*)(vbuf + o));   // read once, overwritten in place
   const VT lc = *(const VT*)(lse2 + ((long long)b * 2 + 1) * nmax + j);
   VT s1, pr, kk, ff;
-  if (scr1) s1 = *(const VT*)(scr1 + (long long)b * n1 + j);
+  if (scr1) s1 = *(const VT*)(scr1 + (long long)b1 * n1 + j);
 #pragma unroll
   for (int e = 0; e < VEC; ++e) {
     const float p = __builtin_amdgcn_exp2f((v[e] - lc[e]) + (v[e] - lr));
@@ -233,14 +236,15 @@ __global__ __launch_bounds__(512) void dsc_split_kernel(const float* __restrict_
 
 // pass 1.  grid: decode_unit_grid(gx = row blocks / 4, NCHUNK_S, B); one wave per 32 rows and one chunk of column tiles.
 // partr[((b*NCHUNK_S + chunk)*n0 + row)] = (0, sum_j 2^v2), partc[((b*nrb + rb)*n1 + j)] = (0, sum over the block's rows)
-// KF: P0 holds the planes of K keyframes, pair b reads those of kf[b]
-template <bool KF>
+// MAP: pair b reads the planes of image b0 in P0 and of image b1 in P1 (pair_rows; P0 == P1 for a shared image set)
+template <int MAP>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void lse_split_kernel(
     const uint4* __restrict__ P0, const uint4* __restrict__ P1, float scale2, float* __restrict__ partr, float* __restrict__ partc,
-    int n0, int n1, int nrb, int ntb, int gx, int nunits, const int* __restrict__ kf, int K) {
-  int bx, by, b, b0;
+    int n0, int n1, int nrb, int ntb, int gx, int nunits, const int* __restrict__ idx0, int N0, const int* __restrict__ idx1,
+    int N1) {
+  int bx, by, b, b0, b1;
   if (!decode_unit_grid(gx, NCHUNK_S, nunits, bx, by, b)) return;
-  if (!kf_row<KF>(kf, K, b, b0)) return;
+  if (!pair_rows<MAP>(idx0, N0, idx1, N1, b, b0, b1)) return;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int l31 = lane & 31, hi = lane >> 5;
   const int rb = bx * 4 + wave, i0 = rb * RT;
@@ -256,7 +260,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   unsigned rowok = 0;
 #pragma unroll
   for (int r = 0; r < 16; ++r) rowok |= (i0 + (r & 3) + 8 * (r >> 2) + 4 * hi < n0 ? 1u : 0u) << r;
-  const uint4* pb = P1 + (long long)b * ntb * SP_BLK_U4;
+  const uint4* pb = P1 + (long long)b1 * ntb * SP_BLK_U4;
   auto tile = [&](const SplitOperand& bt, int jt) {
     const f32x16 acc = corr_split(a, bt);
     const int j = jt * RT + l31;
@@ -314,16 +318,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 // scores = 2^((v2 - lc2) + (v2 - lr2)), kp = scr0 (x) scr1, final = scores kp.
 template <int VEC,   // floats per lane of an output store: 4 when the output rows are 16-byte aligned (n1 % 4 == 0), 2 for even n1
                      // (n1 = 1938, the Map-free grid), else 1
-          bool KF>   // keyframe mode: P0 / scr0 hold K keyframes, pair b reads kf[b]
+          int MAP>   // pair b reads image b0 of P0 / scr0 and image b1 of P1 / scr1 (pair_rows)
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void dual_softmax_split_apply_kernel(
     const uint4* __restrict__ P0, const uint4* __restrict__ P1, float scale2, const float* __restrict__ scr0,
     const float* __restrict__ scr1, const float* __restrict__ lse2, float* __restrict__ scores, float* __restrict__ kp,
-    float* __restrict__ fin, int n0, int n1, int nmax, int nrb, int ntb, int gx, int nunits, int nchunk, const int* __restrict__ kf,
-    int K) {
+    float* __restrict__ fin, int n0, int n1, int nmax, int nrb, int ntb, int gx, int nunits, int nchunk,
+    const int* __restrict__ idx0, int N0, const int* __restrict__ idx1, int N1) {
   __shared__ __attribute__((aligned(16))) float stage[4][RT * 64];
-  int bx, by, b, b0;
+  int bx, by, b, b0, b1;
   if (!decode_unit_grid<true>(gx, nchunk, nunits, bx, by, b)) return;
-  if (!kf_row<KF>(kf, K, b, b0)) return;
+  if (!pair_rows<MAP>(idx0, N0, idx1, N1, b, b0, b1)) return;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int l31 = lane & 31, hi = lane >> 5;
   const int rb = bx * 4 + wave, i0 = rb * RT;
@@ -341,7 +345,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     lr[r] = lse2[((long long)b * 2 + 0) * nmax + ic];
     s0[r] = scr0 ? scr0[(long long)b0 * n0 + ic] : 0.f;
   }
-  const uint4* pb = P1 + (long long)b * ntb * SP_BLK_U4;
+  const uint4* pb = P1 + (long long)b1 * ntb * SP_BLK_U4;
   typedef float VT __attribute__((ext_vector_type(VEC)));
   constexpr int LPR = 64 / VEC, RPI = 64 / LPR;   // lanes per 64-column row, rows per store instruction
   const int dr = lane / LPR, dc = (lane % LPR) * VEC;
@@ -358,7 +362,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       const int j = (jt + t) * RT + l31;
       const int jc = j < n1 ? j : n1 - 1;
       lc[t] = lse2[((long long)b * 2 + 1) * nmax + jc];
-      s1[t] = scr1 ? scr1[(long long)b * n1 + jc] : 0.f;
+      s1[t] = scr1 ? scr1[(long long)b1 * n1 + jc] : 0.f;
     }
     const int jbase = jt * RT;   // first column of the pair of tiles; columns of tile jt + 1 past jt1 / n1 are never stored
     const int jlim = min(n1, min(jt + 2, jt1) * RT);
@@ -397,20 +401,21 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 constexpr int SK_RCH = 256;   // rows per chunk of the column pass
 
 // Z2[(n0+1) x ldz] = couplings * log2(e) (S / sqrt(C), alpha on the last row / column / corner, -1e30 in the row pad)
-// KF: dsc0 holds K keyframes, pair b reads row kf[b]
-template <bool KF>
+// MAP: pair b reads row b0 of dsc0 and row b1 of dsc1 (pair_rows)
+template <int MAP>
 __global__ __launch_bounds__(256) void couplings_kernel(const float* __restrict__ dsc0, const float* __restrict__ dsc1,
                                                         float scale2, float alpha2, float* __restrict__ Z, int C, int n0,
-                                                        int n1, int ldz, const int* __restrict__ kf, int K) {
+                                                        int n1, int ldz, const int* __restrict__ idx0, int N0,
+                                                        const int* __restrict__ idx1, int N1) {
   __shared__ __attribute__((aligned(16))) float sA[CMAX * MT];
   __shared__ __attribute__((aligned(16))) float sB[CMAX * MT];
   const int b = blockIdx.z, i0 = blockIdx.y * MT, j0 = blockIdx.x * MT;
-  int b0;
-  if (!kf_row<KF>(kf, K, b, b0)) return;   // (the whole workgroup: before the barrier)
+  int b0, b1;
+  if (!pair_rows<MAP>(idx0, N0, idx1, N1, b, b0, b1)) return;   // (the whole workgroup: before the barrier)
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, wi = wave >> 1, wj = wave & 1;
   const int l31 = lane & 31, hi = lane >> 5;
   stage_desc(sA, dsc0 + (long long)b0 * C * n0, C, n0, i0);
-  stage_desc(sB, dsc1 + (long long)b * C * n1, C, n1, j0);
+  stage_desc(sB, dsc1 + (long long)b1 * C * n1, C, n1, j0);
   __syncthreads();
   const f32x16 acc = corr_tile(sA, sB, C, wi, wj, lane);
   const int jx = j0 + wj * 32 + l31;
@@ -519,17 +524,18 @@ __global__ __launch_bounds__(256) void sink_col_fin_kernel(const float2* __restr
   v[(long long)b * ldz + j] = j > n1 ? 0.f : (j == n1 ? last2 : norm2) - (m + __builtin_amdgcn_logf(s));
 }
 
-// KF: scr0 holds K keyframes, pair b reads row kf[b]
-template <bool KF>
+// MAP: pair b reads row b0 of scr0 and row b1 of scr1 (pair_rows)
+template <int MAP>
 __global__ __launch_bounds__(256) void sink_final_kernel(const float* __restrict__ Z, const float* __restrict__ u,
                                                          const float* __restrict__ v, float norm2,
                                                          const float* __restrict__ scr0, const float* __restrict__ scr1,
                                                          float* __restrict__ out, float* __restrict__ kp,
                                                          float* __restrict__ fin, int n0, int n1, int ldz, int ldu,
-                                                         const int* __restrict__ kf, int K) {
+                                                         const int* __restrict__ idx0, int N0, const int* __restrict__ idx1,
+                                                         int N1) {
   const int b = blockIdx.z, i = blockIdx.y;
-  int b0;
-  if (!kf_row<KF>(kf, K, b, b0)) return;
+  int b0, b1;
+  if (!pair_rows<MAP>(idx0, N0, idx1, N1, b, b0, b1)) return;
   const int j = blockIdx.x * 256 + threadIdx.x;
   if (j >= n1) return;
   const float z = Z[((long long)b * (n0 + 1) + i) * ldz + j];
@@ -537,7 +543,7 @@ __global__ __launch_bounds__(256) void sink_final_kernel(const float* __restrict
   const long long o = ((long long)b * n0 + i) * n1 + j;
   if (out) out[o] = pr;
   if (scr0) {
-    const float kk = scr0[(long long)b0 * n0 + i] * scr1[(long long)b * n1 + j];
+    const float kk = scr0[(long long)b0 * n0 + i] * scr1[(long long)b1 * n1 + j];
     if (kp) kp[o] = kk;
     if (fin) fin[o] = pr * kk;
   }
@@ -665,13 +671,13 @@ long long mk_dual_softmax_work_floats(int B, int n0, int n1, int own_copy) {
 
 }  // extern "C"
 
-// the exact-fp32 dual softmax; KF: keyframe mode (operand 0 read through kf, mickey_hip.h: mk_dual_softmax_kf).
+// the exact-fp32 dual softmax; MAP / rm: the operand maps (mk_common.hpp: pair_rows; mickey_hip.h: mk_dual_softmax_kf, _pairs).
 // lse_out (training forward, mk::ds::dual_softmax_train_fwd): the merged log2-sums go there instead of `work`, merged with the
 // dustbin read from the device pointer dustbin_dev (use_dustbin / dustbin unused)
-template <bool KF>
+template <int MAP>
 static int dual_softmax_impl(const float* dsc0, const float* dsc1, const float* scr0, const float* scr1, float inv_temperature,
                              int use_dustbin, float dustbin, float* scores, float* kp_scores, float* final_scores, float* work, int B,
-                             int C, int n0, int n1, const int* kf, int K, hipStream_t st, float* lse_out = nullptr,
+                             int C, int n0, int n1, const RowMaps& rm, hipStream_t st, float* lse_out = nullptr,
                              const float* dustbin_dev = nullptr) {
   MK_CHECK_ARG(B > 0 && n0 > 0 && n1 > 0 && C > 0 && C <= CMAX && C % 2 == 0, "mk_dual_softmax: need 0 < C <= %d, C even", CMAX);
   MK_CHECK_ARG((scr0 && scr1) || (!kp_scores && !final_scores), "mk_dual_softmax: kp/final scores need scr0 and scr1");
@@ -688,11 +694,11 @@ static int dual_softmax_impl(const float* dsc0, const float* dsc1, const float* 
   const int gx1 = (n0 + 4 * RT - 1) / (4 * RT);
   const dim3 g1((unsigned)gx1 * NCHUNK * ((B + 7) / 8 * 8));   // see decode_unit_grid
   if (C == CMAX)
-    hipLaunchKernelGGL((lse_partial_kernel<true, KF>), g1, dim3(256), 0, st, dsc0, dsc1, scale2, partr, partc, vbuf, C, n0, n1, nrb, gx1, B,
-                       kf, K);
+    hipLaunchKernelGGL((lse_partial_kernel<true, MAP>), g1, dim3(256), 0, st, dsc0, dsc1, scale2, partr, partc, vbuf, C, n0, n1, nrb, gx1, B,
+                       rm.idx0, rm.N0, rm.idx1, rm.N1);
   else
-    hipLaunchKernelGGL((lse_partial_kernel<false, KF>), g1, dim3(256), 0, st, dsc0, dsc1, scale2, partr, partc, vbuf, C, n0, n1, nrb, gx1, B,
-                       kf, K);
+    hipLaunchKernelGGL((lse_partial_kernel<false, MAP>), g1, dim3(256), 0, st, dsc0, dsc1, scale2, partr, partc, vbuf, C, n0, n1, nrb, gx1, B,
+                       rm.idx0, rm.N0, rm.idx1, rm.N1);
   MK_CHECK_LAUNCH();
   if (lse_out) {
     const int rc = lse_merge_dev(partr, partc, lse2, dustbin_dev, B, n0, n1, nrb, NCHUNK, st);
@@ -707,11 +713,11 @@ static int dual_softmax_impl(const float* dsc0, const float* dsc1, const float* 
     const bool v2 = (n1 % 2 == 0) && ((((uintptr_t)vbuf | (uintptr_t)scores | (uintptr_t)kp_scores | (uintptr_t)final_scores |
                                         (uintptr_t)scr1 | (uintptr_t)lse2) & 7) == 0) && (nmax % 2 == 0);
     if (v2)
-      hipLaunchKernelGGL((dual_softmax_apply_kernel<2, KF>), dim3((n1 / 2 + 255) / 256, n0, B), dim3(256), 0, st, vbuf, scr0, scr1, lse2,
-                         scores, kp_scores, final_scores, n0, n1, nmax, kf, K);
+      hipLaunchKernelGGL((dual_softmax_apply_kernel<2, MAP>), dim3((n1 / 2 + 255) / 256, n0, B), dim3(256), 0, st, vbuf, scr0, scr1, lse2,
+                         scores, kp_scores, final_scores, n0, n1, nmax, rm.idx0, rm.N0, rm.idx1, rm.N1);
     else
-      hipLaunchKernelGGL((dual_softmax_apply_kernel<1, KF>), dim3((n1 + 255) / 256, n0, B), dim3(256), 0, st, vbuf, scr0, scr1, lse2, scores,
-                         kp_scores, final_scores, n0, n1, nmax, kf, K);
+      hipLaunchKernelGGL((dual_softmax_apply_kernel<1, MAP>), dim3((n1 + 255) / 256, n0, B), dim3(256), 0, st, vbuf, scr0, scr1, lse2, scores,
+                         kp_scores, final_scores, n0, n1, nmax, rm.idx0, rm.N0, rm.idx1, rm.N1);
     MK_CHECK_LAUNCH();
   }
   return MK_OK;
@@ -731,50 +737,81 @@ int mk_dual_softmax_kf(const float* dsc0, const float* dsc1, const float* scr0, 
                        int C, int n0, int n1, const int* kf_index, int K, mk_stream_t stream) {
   MK_CHECK_ARG(dsc0 && dsc1 && work, "mk_dual_softmax: null pointer");
   MK_CHECK_ARG(kf_index ? (K > 0 && K <= B) : K == B, "mk_dual_softmax_kf: need 0 < K <= B with a keyframe map, K == B without");
-  if (kf_index)
-    return dual_softmax_impl<true>(dsc0, dsc1, scr0, scr1, inv_temperature, use_dustbin, dustbin, scores, kp_scores, final_scores, work,
-                                   B, C, n0, n1, kf_index, K, (hipStream_t)stream);
-  return dual_softmax_impl<false>(dsc0, dsc1, scr0, scr1, inv_temperature, use_dustbin, dustbin, scores, kp_scores, final_scores, work,
-                                  B, C, n0, n1, nullptr, B, (hipStream_t)stream);
+  return mk_dual_softmax_pairs(dsc0, dsc1, scr0, scr1, inv_temperature, use_dustbin, dustbin, scores, kp_scores, final_scores, work, B,
+                               C, n0, n1, kf_index, nullptr, K, B, stream);
+}
+
+int mk_dual_softmax_pairs(const float* dsc0, const float* dsc1, const float* scr0, const float* scr1, float inv_temperature,
+                          int use_dustbin, float dustbin, float* scores, float* kp_scores, float* final_scores, float* work, int B,
+                          int C, int n0, int n1, const int* idx0, const int* idx1, int N0, int N1, mk_stream_t stream) {
+  MK_CHECK_ARG(dsc0 && dsc1 && work, "mk_dual_softmax_pairs: null pointer");
+  const RowMaps rm{idx0, N0, idx1, N1};
+  if (const int rc = check_row_maps("mk_dual_softmax_pairs", rm, B)) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  switch (rm.mode()) {   // (the instantiations of the plain and the _kf call: the same kernels, the same bits)
+    case MAP_NONE:
+      return dual_softmax_impl<MAP_NONE>(dsc0, dsc1, scr0, scr1, inv_temperature, use_dustbin, dustbin, scores, kp_scores, final_scores,
+                                         work, B, C, n0, n1, rm, st);
+    case MAP_KF:
+      return dual_softmax_impl<MAP_KF>(dsc0, dsc1, scr0, scr1, inv_temperature, use_dustbin, dustbin, scores, kp_scores, final_scores,
+                                       work, B, C, n0, n1, rm, st);
+    default:
+      return dual_softmax_impl<MAP_PAIRS>(dsc0, dsc1, scr0, scr1, inv_temperature, use_dustbin, dustbin, scores, kp_scores,
+                                          final_scores, work, B, C, n0, n1, rm, st);
+  }
+}
+
+// row / column partials + log2-sum-exp vectors of B pairs (the part of the split path's work that is per pair)
+static long long split_pass_floats(int B, int n0, int n1) {
+  const long long nmax = n0 > n1 ? n0 : n1, nrb = (n0 + RT - 1) / RT;
+  return (long long)B * NCHUNK_S * n0 * 2 + (long long)B * nrb * n1 * 2 + (long long)B * 2 * nmax + 8;
 }
 
 long long mk_dual_softmax_split_work_floats(int B, int n0, int n1) {
-  const long long nmax = n0 > n1 ? n0 : n1, nrb = (n0 + RT - 1) / RT, ntb = (n1 + RT - 1) / RT;
+  const long long nrb = (n0 + RT - 1) / RT, ntb = (n1 + RT - 1) / RT;
   // the two split-plane images (16 KiB per block of 32 keypoints) + row / column partials + log2-sum-exp vectors
-  return (long long)B * (nrb + ntb) * SP_BLK_U4 * 4 + (long long)B * NCHUNK_S * n0 * 2 + (long long)B * nrb * n1 * 2 +
-         (long long)B * 2 * nmax + 8;
+  return (long long)B * (nrb + ntb) * SP_BLK_U4 * 4 + split_pass_floats(B, n0, n1);
 }
+
+long long mk_dsc_split_planes_floats(int N, int n) { return (long long)N * ((n + RT - 1) / RT) * SP_BLK_U4 * 4; }
+
+long long mk_dual_softmax_split_pairs_work_floats(int B, int n0, int n1, int N0, int N1, int shared) {
+  return mk_dsc_split_planes_floats(N0, n0) + (shared ? 0 : mk_dsc_split_planes_floats(N1, n1)) + split_pass_floats(B, n0, n1);
+}
+
+long long mk_dual_softmax_split_planes_work_floats(int B, int n0, int n1) { return split_pass_floats(B, n0, n1); }
 
 }  // extern "C"
 
-// the split-fp16 dual softmax; KF: keyframe mode (mickey_hip.h: mk_dual_softmax_split_kf): the planes of operand 0 are made for the
-// K keyframes only (rows [0, K) of P0's B-pair region) and the passes address them through kf
-// lse_out / dustbin_dev: as for dual_softmax_impl
-template <bool KF>
-static int dual_softmax_split_impl(const float* dsc0, const float* dsc1, const float* scr0, const float* scr1, float inv_temperature,
-                                   int use_dustbin, float dustbin, float* scores, float* kp_scores, float* final_scores, float* work,
-                                   int B, int C, int n0, int n1, const int* kf, int K, hipStream_t st, float* lse_out = nullptr,
-                                   const float* dustbin_dev = nullptr) {
+// the host checks of the split-fp16 dual softmax (every entry point of it, before any launch)
+static int split_check_args(float* work, int B, int C, int n0, int n1, const float* scr0, const float* scr1, float inv_temperature,
+                            const float* kp_scores, const float* final_scores) {
   MK_CHECK_ARG(B > 0 && n0 > 0 && n1 > 0 && C == 16 * SP_KS, "mk_dual_softmax_split: C must be %d (use mk_dual_softmax otherwise)", 16 * SP_KS);
   MK_CHECK_ARG((scr0 && scr1) || (!kp_scores && !final_scores), "mk_dual_softmax_split: kp/final scores need scr0 and scr1");
   MK_CHECK_ARG(((uintptr_t)work & 15) == 0, "mk_dual_softmax_split: work must be 16-byte aligned");
-  const float LOG2E = 1.4426950408889634f;
   // unit-norm descriptors: |v2| <= inv_T log2(e); the maximum-free sums of pass 1 need 2^v2 and n 2^v2 inside fp32
-  MK_CHECK_ARG(inv_temperature > 0.f && inv_temperature * LOG2E <= 100.f,
+  MK_CHECK_ARG(inv_temperature > 0.f && inv_temperature * 1.4426950408889634f <= 100.f,
                "mk_dual_softmax_split: temperature %g too small for the maximum-free sums (use mk_dual_softmax)", 1.0 / inv_temperature);
+  return MK_OK;
+}
+
+// the passes of the split-fp16 dual softmax on READY planes P0 / P1 (dsc_split_kernel's; P0 == P1 for a shared image set);
+// MAP / rm: the operand maps (pair_rows).  pass_work: split_pass_floats(B, n0, n1) floats, 16-byte aligned.
+// lse_out / dustbin_dev: as for dual_softmax_impl
+template <int MAP>
+static int split_passes(const uint4* P0, const uint4* P1, const float* scr0, const float* scr1, float inv_temperature, int use_dustbin,
+                        float dustbin, float* scores, float* kp_scores, float* final_scores, float* pass_work, int B, int n0, int n1,
+                        const RowMaps& rm, hipStream_t st, float* lse_out, const float* dustbin_dev) {
+  const float LOG2E = 1.4426950408889634f;
   const int nmax = n0 > n1 ? n0 : n1, nrb = (n0 + RT - 1) / RT, ntb = (n1 + RT - 1) / RT;
-  uint4* P0 = (uint4*)work;
-  uint4* P1 = P0 + (long long)B * nrb * SP_BLK_U4;
-  float* partr = (float*)(P1 + (long long)B * ntb * SP_BLK_U4);
+  float* partr = pass_work;
   float* partc = partr + (long long)B * NCHUNK_S * n0 * 2;
   float* lse2 = lse_out ? lse_out : partc + (long long)B * nrb * n1 * 2;
-  hipLaunchKernelGGL(dsc_split_kernel, dim3(nrb, K), dim3(512), 0, st, dsc0, P0, n0, nrb);
-  hipLaunchKernelGGL(dsc_split_kernel, dim3(ntb, B), dim3(512), 0, st, dsc1, P1, n1, ntb);
-  MK_CHECK_LAUNCH();
   const float scale2 = inv_temperature * LOG2E / (SP_SCALE * SP_SCALE);
   const int gx = (nrb + 3) / 4;
   const dim3 g((unsigned)gx * NCHUNK_S * ((B + 7) / 8 * 8));   // see decode_unit_grid
-  hipLaunchKernelGGL(lse_split_kernel<KF>, g, dim3(256), 0, st, P0, P1, scale2, partr, partc, n0, n1, nrb, ntb, gx, B, kf, K);
+  hipLaunchKernelGGL(lse_split_kernel<MAP>, g, dim3(256), 0, st, P0, P1, scale2, partr, partc, n0, n1, nrb, ntb, gx, B, rm.idx0, rm.N0,
+                     rm.idx1, rm.N1);
   MK_CHECK_LAUNCH();
   if (lse_out) {
     const int rc = lse_merge_dev(partr, partc, lse2, dustbin_dev, B, n0, n1, nrb, NCHUNK_S, st);
@@ -791,17 +828,53 @@ static int dual_softmax_split_impl(const float* dsc0, const float* dsc1, const f
     const dim3 g2((unsigned)gx * nchunk2 * ((B + 7) / 8 * 8));
     const bool a16 = ((((uintptr_t)scores | (uintptr_t)kp_scores | (uintptr_t)final_scores) & 15) == 0);
     if ((n1 & 3) == 0 && a16)
-      hipLaunchKernelGGL((dual_softmax_split_apply_kernel<4, KF>), g2, dim3(256), 0, st, P0, P1, scale2, scr0, scr1, lse2, scores, kp_scores,
-                         final_scores, n0, n1, nmax, nrb, ntb, gx, B, nchunk2, kf, K);
+      hipLaunchKernelGGL((dual_softmax_split_apply_kernel<4, MAP>), g2, dim3(256), 0, st, P0, P1, scale2, scr0, scr1, lse2, scores, kp_scores,
+                         final_scores, n0, n1, nmax, nrb, ntb, gx, B, nchunk2, rm.idx0, rm.N0, rm.idx1, rm.N1);
     else if ((n1 & 1) == 0 && ((((uintptr_t)scores | (uintptr_t)kp_scores | (uintptr_t)final_scores) & 7) == 0))
-      hipLaunchKernelGGL((dual_softmax_split_apply_kernel<2, KF>), g2, dim3(256), 0, st, P0, P1, scale2, scr0, scr1, lse2, scores, kp_scores,
-                         final_scores, n0, n1, nmax, nrb, ntb, gx, B, nchunk2, kf, K);
+      hipLaunchKernelGGL((dual_softmax_split_apply_kernel<2, MAP>), g2, dim3(256), 0, st, P0, P1, scale2, scr0, scr1, lse2, scores, kp_scores,
+                         final_scores, n0, n1, nmax, nrb, ntb, gx, B, nchunk2, rm.idx0, rm.N0, rm.idx1, rm.N1);
     else
-      hipLaunchKernelGGL((dual_softmax_split_apply_kernel<1, KF>), g2, dim3(256), 0, st, P0, P1, scale2, scr0, scr1, lse2, scores, kp_scores,
-                         final_scores, n0, n1, nmax, nrb, ntb, gx, B, nchunk2, kf, K);
+      hipLaunchKernelGGL((dual_softmax_split_apply_kernel<1, MAP>), g2, dim3(256), 0, st, P0, P1, scale2, scr0, scr1, lse2, scores, kp_scores,
+                         final_scores, n0, n1, nmax, nrb, ntb, gx, B, nchunk2, rm.idx0, rm.N0, rm.idx1, rm.N1);
     MK_CHECK_LAUNCH();
   }
   return MK_OK;
+}
+
+static int split_passes_any(const uint4* P0, const uint4* P1, const float* scr0, const float* scr1, float inv_temperature,
+                            int use_dustbin, float dustbin, float* scores, float* kp_scores, float* final_scores, float* pass_work, int B,
+                            int n0, int n1, const RowMaps& rm, hipStream_t st, float* lse_out = nullptr,
+                            const float* dustbin_dev = nullptr) {
+  switch (rm.mode()) {   // (MAP_NONE / MAP_KF: the instantiations of the plain and the _kf call -- the same kernels, the same bits)
+    case MAP_NONE:
+      return split_passes<MAP_NONE>(P0, P1, scr0, scr1, inv_temperature, use_dustbin, dustbin, scores, kp_scores, final_scores, pass_work,
+                                    B, n0, n1, rm, st, lse_out, dustbin_dev);
+    case MAP_KF:
+      return split_passes<MAP_KF>(P0, P1, scr0, scr1, inv_temperature, use_dustbin, dustbin, scores, kp_scores, final_scores, pass_work, B,
+                                  n0, n1, rm, st, lse_out, dustbin_dev);
+    default:
+      return split_passes<MAP_PAIRS>(P0, P1, scr0, scr1, inv_temperature, use_dustbin, dustbin, scores, kp_scores, final_scores, pass_work,
+                                     B, n0, n1, rm, st, lse_out, dustbin_dev);
+  }
+}
+
+// the split-fp16 dual softmax from fp32 descriptors: planes first (of the rm.N0 / rm.N1 images of each operand, ONCE each), then
+// the passes.  work: [planes of operand 0: rows0 images reserved | planes of operand 1 | pass work]; shared: both operands are one
+// image set whose planes are made once and read by both sides (P1 = P0, no second region)
+static int dual_softmax_split_fwd(const float* dsc0, const float* dsc1, const float* scr0, const float* scr1, float inv_temperature,
+                                  int use_dustbin, float dustbin, float* scores, float* kp_scores, float* final_scores, float* work,
+                                  int B, int C, int n0, int n1, const RowMaps& rm, int rows0, bool shared, hipStream_t st,
+                                  float* lse_out = nullptr, const float* dustbin_dev = nullptr) {
+  if (const int rc = split_check_args(work, B, C, n0, n1, scr0, scr1, inv_temperature, kp_scores, final_scores)) return rc;
+  const int nrb = (n0 + RT - 1) / RT, ntb = (n1 + RT - 1) / RT;
+  uint4* P0 = (uint4*)work;
+  uint4* P1 = shared ? P0 : P0 + (long long)rows0 * nrb * SP_BLK_U4;
+  float* pass_work = (float*)(P1 + (long long)(shared ? rm.N0 : rm.N1) * ntb * SP_BLK_U4);
+  hipLaunchKernelGGL(dsc_split_kernel, dim3(nrb, rm.N0), dim3(512), 0, st, dsc0, P0, n0, nrb);
+  if (!shared) hipLaunchKernelGGL(dsc_split_kernel, dim3(ntb, rm.N1), dim3(512), 0, st, dsc1, P1, n1, ntb);
+  MK_CHECK_LAUNCH();
+  return split_passes_any(P0, P1, scr0, scr1, inv_temperature, use_dustbin, dustbin, scores, kp_scores, final_scores, pass_work, B, n0,
+                          n1, rm, st, lse_out, dustbin_dev);
 }
 
 extern "C" {
@@ -818,11 +891,40 @@ int mk_dual_softmax_split_kf(const float* dsc0, const float* dsc1, const float* 
                              int B, int C, int n0, int n1, const int* kf_index, int K, mk_stream_t stream) {
   MK_CHECK_ARG(dsc0 && dsc1 && work, "mk_dual_softmax_split: null pointer");
   MK_CHECK_ARG(kf_index ? (K > 0 && K <= B) : K == B, "mk_dual_softmax_split_kf: need 0 < K <= B with a keyframe map, K == B without");
-  if (kf_index)
-    return dual_softmax_split_impl<true>(dsc0, dsc1, scr0, scr1, inv_temperature, use_dustbin, dustbin, scores, kp_scores, final_scores,
-                                         work, B, C, n0, n1, kf_index, K, (hipStream_t)stream);
-  return dual_softmax_split_impl<false>(dsc0, dsc1, scr0, scr1, inv_temperature, use_dustbin, dustbin, scores, kp_scores, final_scores,
-                                        work, B, C, n0, n1, nullptr, B, (hipStream_t)stream);
+  // (operand 0's planes are made for the K keyframes only; its region keeps B images' room: mk_dual_softmax_split_work_floats)
+  return dual_softmax_split_fwd(dsc0, dsc1, scr0, scr1, inv_temperature, use_dustbin, dustbin, scores, kp_scores, final_scores, work, B,
+                                C, n0, n1, RowMaps{kf_index, K, nullptr, B}, B, false, (hipStream_t)stream);
+}
+
+int mk_dual_softmax_split_pairs(const float* dsc0, const float* dsc1, const float* scr0, const float* scr1, float inv_temperature,
+                                int use_dustbin, float dustbin, float* scores, float* kp_scores, float* final_scores, float* work,
+                                int B, int C, int n0, int n1, const int* idx0, const int* idx1, int N0, int N1, mk_stream_t stream) {
+  MK_CHECK_ARG(dsc0 && dsc1 && work, "mk_dual_softmax_split_pairs: null pointer");
+  const RowMaps rm{idx0, N0, idx1, N1};
+  if (const int rc = check_row_maps("mk_dual_softmax_split_pairs", rm, B)) return rc;
+  const bool shared = dsc0 == dsc1 && n0 == n1 && N0 == N1;   // one image set on both sides: its planes are made once
+  return dual_softmax_split_fwd(dsc0, dsc1, scr0, scr1, inv_temperature, use_dustbin, dustbin, scores, kp_scores, final_scores, work, B,
+                                C, n0, n1, rm, N0, shared, (hipStream_t)stream);
+}
+
+int mk_dsc_split_planes(const float* dsc, float* planes, int N, int C, int n, mk_stream_t stream) {
+  MK_CHECK_ARG(dsc && planes, "mk_dsc_split_planes: null pointer");
+  MK_CHECK_ARG(N > 0 && n > 0 && C == 16 * SP_KS, "mk_dsc_split_planes: need N > 0, n > 0, C == %d", 16 * SP_KS);
+  MK_CHECK_ARG(((uintptr_t)planes & 15) == 0, "mk_dsc_split_planes: planes must be 16-byte aligned");
+  return split_planes(dsc, (uint4*)planes, n, (n + RT - 1) / RT, N, (hipStream_t)stream);
+}
+
+int mk_dual_softmax_split_planes(const float* planes0, const float* planes1, const float* scr0, const float* scr1,
+                                 float inv_temperature, int use_dustbin, float dustbin, float* scores, float* kp_scores,
+                                 float* final_scores, float* work, int B, int n0, int n1, const int* idx0, const int* idx1, int N0,
+                                 int N1, mk_stream_t stream) {
+  MK_CHECK_ARG(planes0 && planes1 && work, "mk_dual_softmax_split_planes: null pointer");
+  MK_CHECK_ARG((((uintptr_t)planes0 | (uintptr_t)planes1) & 15) == 0, "mk_dual_softmax_split_planes: planes must be 16-byte aligned");
+  const RowMaps rm{idx0, N0, idx1, N1};
+  if (const int rc = check_row_maps("mk_dual_softmax_split_planes", rm, B)) return rc;
+  if (const int rc = split_check_args(work, B, 16 * SP_KS, n0, n1, scr0, scr1, inv_temperature, kp_scores, final_scores)) return rc;
+  return split_passes_any((const uint4*)planes0, (const uint4*)planes1, scr0, scr1, inv_temperature, use_dustbin, dustbin, scores,
+                          kp_scores, final_scores, work, B, n0, n1, rm, (hipStream_t)stream);
 }
 
 }  // extern "C"
@@ -839,11 +941,12 @@ int split_planes(const float* dsc, uint4* planes, int n, int nblk, int nimg, hip
 int dual_softmax_train_fwd(int split, const float* dsc0, const float* dsc1, const float* scr0, const float* scr1,
                            float inv_temperature, const float* dustbin, float* scores, float* kp_scores, float* final_scores,
                            float* lse, float* work, int B, int C, int n0, int n1, hipStream_t st) {
+  const RowMaps rm{nullptr, B, nullptr, B};
   if (split)
-    return dual_softmax_split_impl<false>(dsc0, dsc1, scr0, scr1, inv_temperature, 0, 0.f, scores, kp_scores, final_scores, work, B,
-                                          C, n0, n1, nullptr, B, st, lse, dustbin);
-  return dual_softmax_impl<false>(dsc0, dsc1, scr0, scr1, inv_temperature, 0, 0.f, scores, kp_scores, final_scores, work, B, C, n0,
-                                  n1, nullptr, B, st, lse, dustbin);
+    return dual_softmax_split_fwd(dsc0, dsc1, scr0, scr1, inv_temperature, 0, 0.f, scores, kp_scores, final_scores, work, B, C, n0, n1,
+                                  rm, B, false, st, lse, dustbin);
+  return dual_softmax_impl<MAP_NONE>(dsc0, dsc1, scr0, scr1, inv_temperature, 0, 0.f, scores, kp_scores, final_scores, work, B, C, n0,
+                                     n1, rm, st, lse, dustbin);
 }
 
 }  // namespace ds
@@ -863,10 +966,10 @@ long long mk_sinkhorn_work_floats(int B, int n0, int n1) {
 
 }  // extern "C"
 
-// KF: keyframe mode (mickey_hip.h: mk_sinkhorn_kf): operand 0 (dsc0, scr0) read through kf
-template <bool KF>
+// MAP / rm: the operand maps (pair_rows; mickey_hip.h: mk_sinkhorn_kf, mk_sinkhorn_pairs)
+template <int MAP>
 static int sinkhorn_impl(const float* dsc0, const float* dsc1, const float* scr0, const float* scr1, float alpha, int iters, float* scores,
-                         float* kp_scores, float* final_scores, float* work, int B, int C, int n0, int n1, const int* kf, int K,
+                         float* kp_scores, float* final_scores, float* work, int B, int C, int n0, int n1, const RowMaps& rm,
                          hipStream_t st) {
   MK_CHECK_ARG((scr0 && scr1) || (!kp_scores && !final_scores), "mk_sinkhorn: kp/final scores need scr0 and scr1");
   MK_CHECK_ARG(B > 0 && n0 > 0 && n1 > 0 && C > 0 && C <= CMAX && C % 2 == 0 && iters >= 0, "mk_sinkhorn: bad args");
@@ -881,8 +984,8 @@ static int sinkhorn_impl(const float* dsc0, const float* dsc1, const float* scr0
   const float norm = -logf((float)n0 + (float)n1);
   const float norm2 = norm * LOG2E, mu_last2 = (logf((float)n1) + norm) * LOG2E, nu_last2 = (logf((float)n0) + norm) * LOG2E;
   // batch-wide passes, non-temporal reads: cache-sized groups of pairs measured no faster (profiles/r04c_bench_matcher.txt)
-  hipLaunchKernelGGL(couplings_kernel<KF>, dim3((ldz + MT - 1) / MT, (n0 + 1 + MT - 1) / MT, B), dim3(256), 0, st, dsc0, dsc1,
-                     LOG2E / sqrtf((float)C), alpha * LOG2E, Z, C, n0, n1, ldz, kf, K);
+  hipLaunchKernelGGL(couplings_kernel<MAP>, dim3((ldz + MT - 1) / MT, (n0 + 1 + MT - 1) / MT, B), dim3(256), 0, st, dsc0, dsc1,
+                     LOG2E / sqrtf((float)C), alpha * LOG2E, Z, C, n0, n1, ldz, rm.idx0, rm.N0, rm.idx1, rm.N1);
   MK_CHECK_LAUNCH();
   hipLaunchKernelGGL(fill_kernel, dim3((unsigned)(((long long)B * ldu + 255) / 256)), dim3(256), 0, st, u, 0.f, (long long)B * ldu);
   hipLaunchKernelGGL(fill_kernel, dim3((unsigned)(((long long)B * ldz + 255) / 256)), dim3(256), 0, st, v, 0.f, (long long)B * ldz);
@@ -893,8 +996,8 @@ static int sinkhorn_impl(const float* dsc0, const float* dsc1, const float* scr0
     hipLaunchKernelGGL(sink_col_fin_kernel, dim3((ldz + 255) / 256, B), dim3(256), 0, st, part, v, n1, ldz, nrc, norm2, nu_last2);
   }
   MK_CHECK_LAUNCH();
-  hipLaunchKernelGGL(sink_final_kernel<KF>, dim3((n1 + 255) / 256, n0, B), dim3(256), 0, st, Z, u, v, norm2, scr0, scr1, scores,
-                     kp_scores, final_scores, n0, n1, ldz, ldu, kf, K);
+  hipLaunchKernelGGL(sink_final_kernel<MAP>, dim3((n1 + 255) / 256, n0, B), dim3(256), 0, st, Z, u, v, norm2, scr0, scr1, scores,
+                     kp_scores, final_scores, n0, n1, ldz, ldu, rm.idx0, rm.N0, rm.idx1, rm.N1);
   MK_CHECK_LAUNCH();
   return MK_OK;
 }
@@ -911,11 +1014,25 @@ int mk_sinkhorn_kf(const float* dsc0, const float* dsc1, const float* scr0, cons
                    mk_stream_t stream) {
   MK_CHECK_ARG(dsc0 && dsc1 && work && (scores || final_scores), "mk_sinkhorn: null pointer");
   MK_CHECK_ARG(kf_index ? (K > 0 && K <= B) : K == B, "mk_sinkhorn_kf: need 0 < K <= B with a keyframe map, K == B without");
-  if (kf_index)
-    return sinkhorn_impl<true>(dsc0, dsc1, scr0, scr1, alpha, iters, scores, kp_scores, final_scores, work, B, C, n0, n1, kf_index, K,
-                               (hipStream_t)stream);
-  return sinkhorn_impl<false>(dsc0, dsc1, scr0, scr1, alpha, iters, scores, kp_scores, final_scores, work, B, C, n0, n1, nullptr, B,
-                              (hipStream_t)stream);
+  return mk_sinkhorn_pairs(dsc0, dsc1, scr0, scr1, alpha, iters, scores, kp_scores, final_scores, work, B, C, n0, n1, kf_index, nullptr, K,
+                           B, stream);
+}
+
+int mk_sinkhorn_pairs(const float* dsc0, const float* dsc1, const float* scr0, const float* scr1, float alpha, int iters, float* scores,
+                      float* kp_scores, float* final_scores, float* work, int B, int C, int n0, int n1, const int* idx0,
+                      const int* idx1, int N0, int N1, mk_stream_t stream) {
+  MK_CHECK_ARG(dsc0 && dsc1 && work && (scores || final_scores), "mk_sinkhorn_pairs: null pointer");
+  const RowMaps rm{idx0, N0, idx1, N1};
+  if (const int rc = check_row_maps("mk_sinkhorn_pairs", rm, B)) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  switch (rm.mode()) {
+    case MAP_NONE:
+      return sinkhorn_impl<MAP_NONE>(dsc0, dsc1, scr0, scr1, alpha, iters, scores, kp_scores, final_scores, work, B, C, n0, n1, rm, st);
+    case MAP_KF:
+      return sinkhorn_impl<MAP_KF>(dsc0, dsc1, scr0, scr1, alpha, iters, scores, kp_scores, final_scores, work, B, C, n0, n1, rm, st);
+    default:
+      return sinkhorn_impl<MAP_PAIRS>(dsc0, dsc1, scr0, scr1, alpha, iters, scores, kp_scores, final_scores, work, B, C, n0, n1, rm, st);
+  }
 }
 
 int mk_mutual_nn(const float* scores, int* matches, int* count, int* work, int B, int n0, int n1, mk_stream_t stream) {

@@ -3,7 +3,7 @@
 //
 // The reference tiles X/Y 100x for its inner torch.multinomial; the outer one (the exponential-race top-k that picks the
 // correspondence sets) is mk_sampler.hip.  Here:
-//   * mk_gather_backproject(_kf, _bwd): the sampled cells -> 3D correspondences X, Y and their weights.
+//   * mk_gather_backproject(_kf, _pairs, _bwd): the sampled cells -> 3D correspondences X, Y and their weights.
 //   * mk_ransac_hypotheses: a correspondence set (X, Y, w: 56 KB) is staged once in LDS and shared by
 //     all its hypotheses; a hypothesis draws its 3 correspondences ~ w without replacement with three uniforms (prefix
 //     sums of the set's weights in LDS, binary search with the chosen ones masked out = the top-3 of an exponential race,
@@ -38,19 +38,21 @@ __device__ __forceinline__ void inv3(const float* K, float* o) {
   o[6] = Cc * id; o[7] = -(a * h - b * g) * id; o[8] = (a * e - b * d) * id;
 }
 
-// KF (keyframe mode): kps0 / dep0 hold K keyframes, pair b reads row kf[b] (kf_row); K0 stays per pair
-template <bool KF>
+// MAP (mk_common.hpp: pair_rows): pair b reads row b0 of kps0 / dep0 and row b1 of kps1 / dep1 (keyframe mode: operand 0 through
+// idx0; pair-list mode: a map on each side); K0 / K1 stay per pair
+template <int MAP>
 __global__ __launch_bounds__(256) void gather_backproject_kernel(const int* __restrict__ idx, const float* __restrict__ fs,
                                                                  const float* __restrict__ kps0, const float* __restrict__ dep0,
                                                                  const float* __restrict__ kps1, const float* __restrict__ dep1,
                                                                  const float* __restrict__ K0, const float* __restrict__ K1,
                                                                  float* __restrict__ X, float* __restrict__ Y,
                                                                  float* __restrict__ wts, float* __restrict__ corr,
-                                                                 int rows_per_pair, int k, int n0, int n1, const int* __restrict__ kf,
-                                                                 int K) {
+                                                                 int rows_per_pair, int k, int n0, int n1,
+                                                                 const int* __restrict__ idx0, int N0, const int* __restrict__ idx1,
+                                                                 int N1) {
   const int r = blockIdx.y, b = r / rows_per_pair;
-  int b0;
-  if (!kf_row<KF>(kf, K, b, b0)) return;
+  int b0, b1;
+  if (!pair_rows<MAP>(idx0, N0, idx1, N1, b, b0, b1)) return;
   const int s = blockIdx.x * 256 + threadIdx.x;
   if (s >= k) return;
   float Ki0[9], Ki1[9];
@@ -59,7 +61,7 @@ __global__ __launch_bounds__(256) void gather_backproject_kernel(const int* __re
   const int c = idx[(long long)r * k + s];
   const int i = c / n1, j = c - i * n1;
   const float u0 = kps0[((long long)b0 * 2 + 0) * n0 + i], v0 = kps0[((long long)b0 * 2 + 1) * n0 + i], d0 = dep0[(long long)b0 * n0 + i];
-  const float u1 = kps1[((long long)b * 2 + 0) * n1 + j], v1 = kps1[((long long)b * 2 + 1) * n1 + j], d1 = dep1[(long long)b * n1 + j];
+  const float u1 = kps1[((long long)b1 * 2 + 0) * n1 + j], v1 = kps1[((long long)b1 * 2 + 1) * n1 + j], d1 = dep1[(long long)b1 * n1 + j];
   const long long o = (long long)r * k + s;
 #pragma unroll
   for (int a = 0; a < 3; ++a) {
@@ -593,13 +595,34 @@ int mk_gather_backproject_kf(const int* idx, const float* final_scores, const fl
                "mk_gather_backproject: null pointer");
   MK_CHECK_ARG(B > 0 && rows_per_pair > 0 && k > 0 && n0 > 0 && n1 > 0, "mk_gather_backproject: bad sizes");
   MK_CHECK_ARG(kf_index ? (K > 0 && K <= B) : K == B, "mk_gather_backproject_kf: need 0 < K <= B with a keyframe map, K == B without");
+  return mk_gather_backproject_pairs(idx, final_scores, kps0, depth0, kps1, depth1, K0, K1, X, Y, wts, corr, B, rows_per_pair, k, n0, n1,
+                                     kf_index, nullptr, K, B, stream);
+}
+
+int mk_gather_backproject_pairs(const int* idx, const float* final_scores, const float* kps0, const float* depth0, const float* kps1,
+                                const float* depth1, const float* K0, const float* K1, float* X, float* Y, float* wts, float* corr,
+                                int B, int rows_per_pair, int k, int n0, int n1, const int* idx0, const int* idx1, int N0, int N1,
+                                mk_stream_t stream) {
+  MK_CHECK_ARG(idx && final_scores && kps0 && depth0 && kps1 && depth1 && K0 && K1 && X && Y && wts && corr,
+               "mk_gather_backproject_pairs: null pointer");
+  MK_CHECK_ARG(B > 0 && rows_per_pair > 0 && k > 0 && n0 > 0 && n1 > 0, "mk_gather_backproject_pairs: bad sizes");
+  const RowMaps rm{idx0, N0, idx1, N1};
+  if (const int rc = check_row_maps("mk_gather_backproject_pairs", rm, B)) return rc;
   const dim3 g((k + 255) / 256, B * rows_per_pair);
-  if (kf_index)
-    hipLaunchKernelGGL(gather_backproject_kernel<true>, g, dim3(256), 0, (hipStream_t)stream, idx, final_scores, kps0, depth0, kps1,
-                       depth1, K0, K1, X, Y, wts, corr, rows_per_pair, k, n0, n1, kf_index, K);
-  else
-    hipLaunchKernelGGL(gather_backproject_kernel<false>, g, dim3(256), 0, (hipStream_t)stream, idx, final_scores, kps0, depth0, kps1,
-                       depth1, K0, K1, X, Y, wts, corr, rows_per_pair, k, n0, n1, nullptr, B);
+  hipStream_t st = (hipStream_t)stream;
+  switch (rm.mode()) {   // (MAP_NONE / MAP_KF: the instantiations of the plain and the _kf call)
+    case MAP_NONE:
+      hipLaunchKernelGGL(gather_backproject_kernel<MAP_NONE>, g, dim3(256), 0, st, idx, final_scores, kps0, depth0, kps1, depth1, K0, K1,
+                         X, Y, wts, corr, rows_per_pair, k, n0, n1, idx0, N0, idx1, N1);
+      break;
+    case MAP_KF:
+      hipLaunchKernelGGL(gather_backproject_kernel<MAP_KF>, g, dim3(256), 0, st, idx, final_scores, kps0, depth0, kps1, depth1, K0, K1, X,
+                         Y, wts, corr, rows_per_pair, k, n0, n1, idx0, N0, idx1, N1);
+      break;
+    default:
+      hipLaunchKernelGGL(gather_backproject_kernel<MAP_PAIRS>, g, dim3(256), 0, st, idx, final_scores, kps0, depth0, kps1, depth1, K0, K1,
+                         X, Y, wts, corr, rows_per_pair, k, n0, n1, idx0, N0, idx1, N1);
+  }
   MK_CHECK_LAUNCH();
   return MK_OK;
 }

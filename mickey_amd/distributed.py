@@ -18,14 +18,33 @@ def shard_range(n_items, rank, world):
 KEYFRAME_KEYS = ("image0", "kps0", "depth_kp0", "scr0", "dsc0", "depth0_map")
 
 
+# per-image entries of a pair-list data dict (model.py: N rows; pair_index and the per-pair entries have P)
+PAIRLIST_KEYS = ("images", "K_color", "kps", "depth_kp", "scr", "dsc", "depth_map")
+
+
+def _pair_list(data):
+    import numpy as np
+    pi = data["pair_index"]
+    pi = (pi.detach().cpu().numpy() if torch.is_tensor(pi) else np.asarray(pi)).astype(np.int64)
+    if pi.ndim != 2 or pi.shape[1] != 2:
+        raise ValueError("pair_index must have shape [P, 2], got %s" % (tuple(pi.shape),))
+    return pi
+
+
 def num_pairs(data):
-    """Pairs in a data dict: image1's rows (keyframe mode: image0 holds the K keyframes) -- image0's otherwise."""
+    """Pairs in a data dict: pair_index's rows in pair-list mode, image1's rows otherwise (keyframe mode: image0 holds the K
+    keyframes)."""
+    if "pair_index" in data:
+        return _pair_list(data).shape[0]
     return data["image1" if "keyframe_index" in data else "image0"].shape[0]
 
 
 def shard_batch(data, rank, world):
     """Slice every batched tensor / list of a data dict to this rank's pairs.  Keyframe mode (data["keyframe_index"]): the rank
-    keeps only the keyframes its pairs use, in order of first use, and its keyframe_index is remapped onto them."""
+    keeps only the keyframes its pairs use, in order of first use, and its keyframe_index is remapped onto them.  Pair-list mode
+    (data["pair_index"]): a contiguous slice of the pair list, and of the image set only the images those pairs use."""
+    if "pair_index" in data:
+        return _shard_pairlist_batch(data, rank, world)
     if "keyframe_index" in data:
         return _shard_keyframe_batch(data, rank, world)
     B = data["image0"].shape[0]
@@ -64,6 +83,31 @@ def _shard_keyframe_batch(data, rank, world):
         elif torch.is_tensor(v) and v.dim() > 0 and v.shape[0] == B:
             out[k] = v[lo:hi]
         elif isinstance(v, (list, tuple)) and len(v) == B:
+            out[k] = v[lo:hi]
+        else:
+            out[k] = v
+    out["pair_base"] = int(data.get("pair_base", 0)) + lo
+    return out
+
+
+def _shard_pairlist_batch(data, rank, world):
+    """The rank's contiguous slice of pair_index; of the image set (images, K_color, any per-image output) only the images its
+    pairs use, in order of first use, with the slice remapped onto them; per-pair entries sliced; pair_base advanced."""
+    pi = _pair_list(data)
+    P, N = pi.shape[0], data["images"].shape[0]
+    lo, hi = shard_range(P, rank, world)
+    used = {}
+    local = [[used.setdefault(int(i), len(used)) for i in row] for row in pi[lo:hi].tolist()]
+    keep = list(used)   # global image of each local one
+    out = {}
+    for k, v in data.items():
+        if k == "pair_index":
+            out[k] = torch.tensor(local, dtype=torch.int64).reshape(hi - lo, 2)
+        elif k in PAIRLIST_KEYS and torch.is_tensor(v) and v.dim() > 0 and v.shape[0] == N:
+            out[k] = v[torch.tensor(keep, dtype=torch.long, device=v.device)]
+        elif torch.is_tensor(v) and v.dim() > 0 and v.shape[0] == P:
+            out[k] = v[lo:hi]
+        elif isinstance(v, (list, tuple)) and len(v) == P:
             out[k] = v[lo:hi]
         else:
             out[k] = v
@@ -144,7 +188,7 @@ def forward_local(model, local, sizes, gatherer=None):
         R, t = model(local)
         conf = local["inliers"]
     else:
-        R, t, conf = _empty_poses(local["image0"].device)
+        R, t, conf = _empty_poses(local["images" if "pair_index" in local else "image0"].device)
         local["R"], local["t"], local["inliers"] = R, t, conf
     if gatherer is not None:
         return gatherer.wait(gatherer.submit(R, t, conf, sizes))
@@ -167,7 +211,7 @@ def forward_sharded(model, data, return_local=False, gatherer=None):
         try:
             dev = next(model.parameters()).device
         except (StopIteration, AttributeError):
-            dev = data["image0"].device
+            dev = data["images" if "pair_index" in data else "image0"].device
         R, t, conf = _empty_poses(dev)
         local["R"], local["t"], local["inliers"] = R, t, conf
     if gatherer is not None:

@@ -354,7 +354,103 @@ class MickeyRelativePose(nn.Module):
             return sol["R"], sol["t"], sol["inliers"], pipeline.inliers_list(sol)
         return sol["R"], sol["t"], sol["inliers"]
 
+    # ---- pair-list mode ---------------------------------------------------------------------------
+    def _pairlist_inputs(self, data):
+        """Pair-list mode (data["pair_index"]): every host check of the mode, before anything is launched (ValueError).  A pair
+        list given as a device tensor is copied to the host for the check: one synchronisation.  -> (pair list as a numpy int32
+        array [P, 2], N, P)."""
+        from . import ops
+        for k in ("image0", "image1", "keyframe_index"):
+            if k in data:
+                raise ValueError("pair-list mode (data['pair_index']) takes data['images'], not data[%r]" % k)
+        for k in ("images", "K_color"):
+            if not torch.is_tensor(data.get(k)):
+                raise ValueError("pair-list mode needs the tensor data[%r]" % k)
+        images, K = data["images"], data["K_color"]
+        if images.dim() != 4 or images.shape[1] != 3 or images.shape[0] == 0:
+            raise ValueError("data['images'] must be [N, 3, H, W] with N >= 1 (one size for the whole set), got %s" % (tuple(images.shape),))
+        N = int(images.shape[0])
+        if tuple(K.shape) != (N, 3, 3):
+            raise ValueError("data['K_color'] must hold one 3x3 matrix per image [%d, 3, 3], got %s" % (N, tuple(K.shape)))
+        pi = data["pair_index"]
+        P = int(pi.shape[0]) if hasattr(pi, "shape") and len(pi.shape) else len(pi)
+        if P == 0:
+            raise ValueError("pair_index holds no pair")
+        int(data.get("pair_base", 0))
+        return ops.check_pair_index(pi, P, N), N, P
+
+    @torch.no_grad()
+    def _forward_pairlist(self, data, return_inliers=False):
+        """Pair-list mode (README "Pair-list mode"): data["images"] [N, 3, H, W] are encoded ONCE (chunks of
+        AMD.IMAGE_CHUNK images; an image no pair uses is still encoded), then pair p = (images[pair_index[p, 0]],
+        images[pair_index[p, 1]]) is matched and solved (chunks of AMD.PAIR_CHUNK pairs on one chunk-sized workspace).  Every
+        pair's result is, bit for bit, that of the standard forward on the materialised batch: one Philox call number for the
+        whole forward, chunk c keyed by its global pair index, one invalid word and one mk_pose_finalize over all P poses."""
+        import numpy as np
+        from . import ops
+        host, N, P = self._pairlist_inputs(data)
+        W = self.device_weights()
+        dev, amd = self._anchor.device, self.cfg["AMD"]
+        ichunk, pchunk = max(1, int(amd.get("IMAGE_CHUNK", 64))), max(1, int(amd.get("PAIR_CHUNK", 32)))
+        keep = bool(amd.get("PAIRLIST_SCORES", False))
+        images = data["images"].to(device=dev, dtype=torch.float32)
+        images = images if images.stride(3) == 1 else images.contiguous()
+        K = data["K_color"].to(device=dev, dtype=torch.float32).contiguous()
+        maps = torch.from_numpy(np.ascontiguousarray(host.T)).to(dev)   # [2, P]: the two maps of the *_pairs entry points
+        if self.heads_split and self._sat_flag is None:   # (see compute_correspondences)
+            self._sat_flag = torch.zeros((1,), device=dev, dtype=torch.int32)
+        self._ws.sat_flag = self._sat_flag if self.heads_split else None
+        parts = []
+        for lo in range(0, N, ichunk):
+            im = images[lo:lo + ichunk]
+            feat, gh, gw = pipeline.encoder_forward(W, self._ws, im)
+            parts.append(pipeline.heads_forward(W, self._ws, feat, im.shape[0], gh, gw, self.cfg))   # fresh tensors, not workspace
+        scr, kps, depth, dsc = parts[0] if len(parts) == 1 else tuple(torch.cat(c, 0) for c in zip(*parts))
+        data["kps_shape"] = [gh, gw]
+        data["depth_map"] = depth.reshape(N, 1, gh, gw)
+        data["kps"], data["depth_kp"], data["scr"], data["dsc"] = kps, depth, scr, dsc
+        data["down_factor"] = self.cfg["MICKEY"]["DINOV2"]["DOWN_FACTOR"]
+        K0, K1 = K.index_select(0, maps[0].long()), K.index_select(0, maps[1].long())
+        data["K_color0"], data["K_color1"] = K0, K1
+        n = dsc.shape[2]
+        planes = None
+        if pipeline.match_uses_split(self.cfg, dsc.shape[1]):   # the set's split planes: once, not per chunk of pairs
+            planes = (ops.dsc_split_planes(dsc),) * 2
+        # the dense matrices: [P, n, n] outputs under AMD.PAIRLIST_SCORES, else only final_scores, in a chunk-sized buffer
+        names = ("scores", "kp_scores", "final_scores")
+        wants = (keep and not self.lean, keep and not self.lean, True)
+        if keep:
+            full = [torch.empty((P, n, n), device=dev, dtype=torch.float32) if w else None for w in wants]
+        else:
+            full = [self._ws.get("pairlist_" + nm, (min(pchunk, P), n, n), torch.float32, dev) if w else None for nm, w in zip(names, wants)]
+        if self._ctr is None:
+            self._ctr = torch.full((1,), 2 * self._calls, device=dev, dtype=torch.int64)
+        self._calls += 1
+        ops.counter_add(self._ctr, 2)   # ONE call number for the forward, as one standard forward over the P pairs takes
+        invalid = torch.zeros((1,), device=dev, dtype=torch.int32)
+        pair_base = int(data.get("pair_base", 0))
+        sols = []
+        for c0 in range(0, P, pchunk):
+            c1 = min(P, c0 + pchunk)
+            out = tuple(None if t is None else (t[c0:c1] if keep else t[:c1 - c0]) for t in full)
+            pi = (maps[0, c0:c1], maps[1, c0:c1])
+            fin = pipeline.match(W, self.cfg, dsc, dsc, scr, scr, not wants[0], pair_index=pi, planes=planes, out=out)[2]
+            sol = pipeline.solve(self.cfg, fin, kps, depth, kps, depth, K0[c0:c1], K1[c0:c1], seed=self.seed, offset=0,
+                                 offset_dev=self._ctr, pair_base=pair_base + c0, ws=self._ws, pair_index=pi, invalid=invalid,
+                                 finalize=False)
+            sols.append(sol if return_inliers else {k: sol[k] for k in ("R", "t", "inliers")})
+        R, t, conf = (sols[0][k] if len(sols) == 1 else torch.cat([s[k] for s in sols], 0) for k in ("R", "t", "inliers"))
+        ops.pose_finalize(R, t, conf, invalid)   # the batch-level rule of the standard forward: any invalid pair zeroes all P poses
+        if keep:
+            data.update({nm: t_ for nm, t_ in zip(names, full) if t_ is not None})
+        if return_inliers:
+            data["inliers_list"] = [m for s in sols for m in pipeline.inliers_list(s)]
+        data["R"], data["t"], data["inliers"] = R, t, conf
+        return R, t
+
     def _forward_eager(self, data, return_inliers=False):
+        if "pair_index" in data:
+            return self._forward_pairlist(data, return_inliers)
         kf = self._keyframe_map(data)   # keyframe mode: the map is checked on the host before any launch
         self.compute_correspondences(data, _kf=kf)   # a missing / failing HIP library raises _native.MickeyHipError: never papered over
         res = self.estimate_pose(data, return_inliers, _kf=kf)
@@ -383,6 +479,8 @@ class MickeyRelativePose(nn.Module):
         if mode is False or str(mode).lower() in ("false", "0", "off") or return_inliers:
             return False
         if "keyframe_index" in data:   # keyframe mode runs eager (K == B would pass the shape test below)
+            return False
+        if "pair_index" in data:   # pair-list mode runs eager too
             return False
         if self._anchor.device.type != "cuda" or not all(torch.is_tensor(data.get(k)) for k in self._GRAPH_INPUTS):
             return False

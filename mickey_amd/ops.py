@@ -782,19 +782,127 @@ def _kf_arg(keyframe_index, B, K, dev):
     return t, K
 
 
+def check_pair_index(index, P, N):
+    """Host validation of a pair list (pair-list mode, mickey_hip.h: the *_pairs entry points): [P, 2] integers, column 0 in
+    [0, N0) and column 1 in [0, N1), where N is the size of the one image set both columns index or an (N0, N1) pair.  Accepts a
+    list, a numpy array or a CPU / device integer tensor (a device tensor is copied to the host: one synchronisation).  Returns
+    the list as a numpy int32 array [P, 2]; raises ValueError on a wrong shape, a non-integer dtype or an entry out of range.
+    Duplicated pairs and self pairs (i, i) are legal, and so is an image no pair uses."""
+    if torch.is_tensor(index):
+        if index.dtype.is_floating_point or index.dtype.is_complex or index.dtype == torch.bool:
+            raise ValueError("pair_index must hold integers, got %s" % index.dtype)
+        a = index.detach().cpu().numpy()
+    else:
+        a = np.asarray(index)
+        if a.size == 0 and a.dtype == np.float64:   # [] -> an empty integer list (the shape check below decides)
+            a = a.astype(np.int64)
+        if a.dtype.kind not in "iu":
+            raise ValueError("pair_index must hold integers, got %s" % a.dtype)
+    if a.ndim != 2 or a.shape != (int(P), 2):
+        raise ValueError("pair_index must have shape [%d, 2] (one (image 0, image 1) row per pair), got %s" % (int(P), tuple(a.shape)))
+    for side, n in enumerate(N if isinstance(N, (tuple, list)) else (N, N)):
+        col = a[:, side]
+        if int(n) <= 0:
+            raise ValueError("pair-list mode needs at least one image on side %d, got %d" % (side, int(n)))
+        if col.size and (int(col.min()) < 0 or int(col.max()) >= int(n)):
+            raise ValueError("pair_index[:, %d] entries must lie in [0, %d), got [%d, %d]" % (side, int(n), int(col.min()), int(col.max())))
+    return a.astype(np.int32)
+
+
+def pair_maps(pair_index, P, N, dev):
+    """[P, 2] pair list (anything check_pair_index takes, validated here on the host) -> the two contiguous int32 device maps
+    (idx0, idx1) of the *_pairs entry points (mickey_hip.h)."""
+    t = torch.from_numpy(np.ascontiguousarray(check_pair_index(pair_index, P, N).T)).to(dev)
+    return t[0], t[1]
+
+
+def _pair_arg(pair_index, N0, N1, dev, P=None):
+    """-> (idx0, idx1, P) for the *_pairs entry points.  A 2-tuple (idx0, idx1) of contiguous int32 device maps -- either may be
+    None = the identity on that side -- is passed as it is (the caller validated it: pipeline / model; a kernel skips a pair whose
+    entry is outside its operand's rows and reads nothing for it).  Anything else is a [P, 2] list, validated on the host here
+    (check_pair_index) and uploaded."""
+    if isinstance(pair_index, tuple) and len(pair_index) == 2 and all(
+            m is None or (torch.is_tensor(m) and m.is_cuda and m.dtype == torch.int32 and m.is_contiguous() and m.dim() == 1)
+            for m in pair_index):
+        i0, i1 = pair_index
+        sizes = {int(m.shape[0]) for m in (i0, i1) if m is not None}
+        sizes |= {int(n) for m, n in ((i0, N0), (i1, N1)) if m is None}   # an identity side has one row per pair
+        if P is not None:
+            sizes.add(int(P))
+        if len(sizes) != 1:
+            raise ValueError("pair maps, identity sides and the pair count disagree: %s" % sorted(sizes))
+        return i0, i1, sizes.pop()
+    n = len(pair_index) if P is None else int(P)
+    i0, i1 = pair_maps(pair_index, n, (N0, N1), dev)
+    return i0, i1, n
+
+
+def _one_mode(keyframe_index, pair_index):
+    if keyframe_index is not None and pair_index is not None:
+        raise ValueError("keyframe_index and pair_index are mutually exclusive")
+
+
+def _outs(out, shape, wants, dev):
+    """The three [B, n0, n1] outputs of a matcher: fresh, or the caller's (out = (scores, kp_scores, final_scores), an entry
+    None where not wanted: a chunked caller writes every chunk into its own buffers)."""
+    if out is None:
+        return [torch.empty(shape, device=dev, dtype=torch.float32) if w else None for w in wants]
+    for o, w in zip(out, wants):
+        if (o is not None) != bool(w) or (o is not None and not (o.is_cuda and o.dtype == torch.float32 and o.is_contiguous() and
+                                                                   tuple(o.shape) == tuple(shape))):
+            raise ValueError("out= must hold a contiguous fp32 device tensor %s exactly where an output is wanted" % (tuple(shape),))
+    return list(out)
+
+
+def dsc_split_planes(dsc):
+    """mk_dsc_split_planes: fp32 [N, 128, n] unit-norm descriptors -> their split-fp16 operand planes (an opaque fp32 buffer),
+    made once for a set that many pairs read (dual_softmax(..., planes=...))."""
+    _chk(dsc, torch.float32)
+    N, C, n = dsc.shape
+    planes = torch.empty((query("mk_dsc_split_planes_floats", N, n),), device=dsc.device, dtype=torch.float32)
+    call("mk_dsc_split_planes", ptr(dsc), ptr(planes), N, C, n, stream())
+    return planes
+
+
 def dual_softmax(dsc0, dsc1, scr0=None, scr1=None, temperature=0.1, dustbin=None, want_scores=True, want_kp=True,
-                 want_final=True, split=False, keyframe_index=None):
+                 want_final=True, split=False, keyframe_index=None, pair_index=None, planes=None, out=None):
     """Returns (scores, kp_scores, final_scores) (None where not requested).  split: the correlation on the 16-bit matrix
     cores with split-fp16 operands (mk_dual_softmax_split; unit-norm descriptors only), else the exact fp32 MFMA.
     keyframe_index (keyframe mode): B pair -> keyframe entries; dsc0 / scr0 then hold the K keyframes, dsc1 / scr1 the B
-    pairs' query frames, and pair b correlates dsc0[keyframe_index[b]] with dsc1[b] (mk_dual_softmax_kf / _split_kf)."""
+    pairs' query frames, and pair b correlates dsc0[keyframe_index[b]] with dsc1[b] (mk_dual_softmax_kf / _split_kf).
+    pair_index (pair-list mode, mk_dual_softmax_pairs / _split_pairs): [P, 2]; dsc0 / scr0 hold N0 images, dsc1 / scr1 N1 (the
+    same tensors for one image set), and pair p correlates dsc0[pair_index[p, 0]] with dsc1[pair_index[p, 1]]; or the 2-tuple of
+    device maps _pair_arg describes.  planes (split, pair-list mode): (planes0, planes1) of dsc_split_planes -- the passes run
+    on them (mk_dual_softmax_split_planes) instead of making the planes in this call.  out: see _outs."""
+    _one_mode(keyframe_index, pair_index)
     _chk(dsc0, torch.float32)
     _chk(dsc1, torch.float32)
     K, C, n0 = dsc0.shape
     B, n1 = dsc1.shape[0], dsc1.shape[2]
+    dev = dsc0.device
+    if pair_index is not None:
+        i0, i1, P = _pair_arg(pair_index, K, B, dev)
+        scores, kp, fin = _outs(out, (P, n0, n1), (want_scores, want_kp and scr0 is not None, want_final and scr0 is not None), dev)
+        args = (ptr(scr0), ptr(scr1), 1.0 / float(temperature), int(dustbin is not None), float(dustbin) if dustbin is not None else 0.0,
+                ptr(scores), ptr(kp), ptr(fin))
+        maps = (ptr(i0), ptr(i1), K, B, stream())
+        if split and planes is not None:
+            work = torch.empty((query("mk_dual_softmax_split_planes_work_floats", P, n0, n1),), device=dev, dtype=torch.float32)
+            call("mk_dual_softmax_split_planes", ptr(planes[0]), ptr(planes[1]), *args, ptr(work), P, n0, n1, *maps)
+        elif split:
+            shared = dsc0.data_ptr() == dsc1.data_ptr() and n0 == n1 and K == B
+            work = torch.empty((query("mk_dual_softmax_split_pairs_work_floats", P, n0, n1, K, B, int(shared)),), device=dev,
+                               dtype=torch.float32)
+            call("mk_dual_softmax_split_pairs", ptr(dsc0), ptr(dsc1), *args, ptr(work), P, C, n0, n1, *maps)
+        else:
+            work = torch.empty((query("mk_dual_softmax_work_floats", P, n0, n1, int(scores is None and fin is None)),), device=dev,
+                               dtype=torch.float32)
+            call("mk_dual_softmax_pairs", ptr(dsc0), ptr(dsc1), *args, ptr(work), P, C, n0, n1, *maps)
+        return scores, kp, fin
+    if planes is not None or out is not None:
+        raise ValueError("planes= and out= belong to pair-list mode (pair_index=)")
     if keyframe_index is None:
         assert K == B, "dsc0 and dsc1 hold different batch counts (keyframe mode needs keyframe_index)"
-    dev = dsc0.device
     kf, kfn = _kf_arg(keyframe_index, B, K, dev)
     mk = lambda want: torch.empty((B, n0, n1), device=dev, dtype=torch.float32) if want else None  # noqa: E731
     scores = mk(want_scores)
@@ -851,14 +959,24 @@ def dual_softmax_bwd(dsc0, dsc1, scr0, scr1, temperature, dustbin, lse, G, split
 
 
 def sinkhorn(dsc0, dsc1, alpha, iters=10, scr0=None, scr1=None, want_scores=True, want_kp=False, want_final=False,
-             keyframe_index=None):
+             keyframe_index=None, pair_index=None, out=None):
     """Returns scores, or (scores, kp_scores, final_scores) when scr0/scr1 are given.  keyframe_index: as in dual_softmax
-    (mk_sinkhorn_kf)."""
+    (mk_sinkhorn_kf); pair_index and out: as in dual_softmax (mk_sinkhorn_pairs)."""
+    _one_mode(keyframe_index, pair_index)
     K, C, n0 = dsc0.shape
     B, n1 = dsc1.shape[0], dsc1.shape[2]
+    dev = dsc0.device
+    if pair_index is not None:
+        i0, i1, P = _pair_arg(pair_index, K, B, dev)
+        res, kp, fin = _outs(out, (P, n0, n1), (want_scores, want_kp and scr0 is not None, want_final and scr0 is not None), dev)
+        work = torch.empty((query("mk_sinkhorn_work_floats", P, n0, n1),), device=dev, dtype=torch.float32)
+        call("mk_sinkhorn_pairs", ptr(dsc0), ptr(dsc1), ptr(scr0), ptr(scr1), float(alpha), int(iters), ptr(res), ptr(kp), ptr(fin),
+             ptr(work), P, C, n0, n1, ptr(i0), ptr(i1), K, B, stream())
+        return res if scr0 is None else (res, kp, fin)
+    if out is not None:
+        raise ValueError("out= belongs to pair-list mode (pair_index=)")
     if keyframe_index is None:
         assert K == B, "dsc0 and dsc1 hold different batch counts (keyframe mode needs keyframe_index)"
-    dev = dsc0.device
     kf, kfn = _kf_arg(keyframe_index, B, K, dev)
     mk = lambda want: torch.empty((B, n0, n1), device=dev, dtype=torch.float32) if want else None  # noqa: E731
     out, kp, fin = mk(want_scores), mk(want_kp and scr0 is not None), mk(want_final and scr0 is not None)
@@ -939,13 +1057,17 @@ def _c(*ts):
     return [None if t is None else t.contiguous() for t in ts]
 
 
-def gather_backproject(idx, final_scores, kps0, depth0, kps1, depth1, K0, K1, rows_per_pair, keyframe_index=None):
+def gather_backproject(idx, final_scores, kps0, depth0, kps1, depth1, K0, K1, rows_per_pair, keyframe_index=None, pair_index=None):
     """keyframe_index (keyframe mode, mk_gather_backproject_kf): kps0 / depth0 hold the K keyframes, pair b reads row
-    keyframe_index[b]; K0 stays per pair."""
+    keyframe_index[b]; K0 stays per pair.  pair_index (pair-list mode, mk_gather_backproject_pairs; forms as in dual_softmax):
+    kps0 / depth0 hold N0 images and kps1 / depth1 N1, pair p reads rows pair_index[p]; K0, K1 stay per pair."""
+    _one_mode(keyframe_index, pair_index)
     idx, final_scores, kps0, depth0, kps1, depth1, K0, K1 = _c(idx, final_scores, kps0, depth0, kps1, depth1, K0, K1)
     B, n0, n1 = final_scores.shape
     R, k = idx.shape
     dev = idx.device
+    if pair_index is not None:
+        i0, i1, _ = _pair_arg(pair_index, kps0.shape[0], kps1.shape[0], dev, P=B)
     kf, kfn = _kf_arg(keyframe_index, B, kps0.shape[0], dev)
     X = torch.empty((R, k, 3), device=dev, dtype=torch.float32)
     Y = torch.empty((R, k, 3), device=dev, dtype=torch.float32)
@@ -953,7 +1075,9 @@ def gather_backproject(idx, final_scores, kps0, depth0, kps1, depth1, K0, K1, ro
     corr = torch.empty((R, k, 6), device=dev, dtype=torch.float32)
     args = (ptr(idx), ptr(final_scores), ptr(kps0), ptr(depth0), ptr(kps1), ptr(depth1), ptr(K0), ptr(K1), ptr(X), ptr(Y),
             ptr(wts), ptr(corr), B, rows_per_pair, k, n0, n1)
-    if kf is None:
+    if pair_index is not None:
+        call("mk_gather_backproject_pairs", *args, ptr(i0), ptr(i1), kps0.shape[0], kps1.shape[0], stream())
+    elif kf is None:
         call("mk_gather_backproject", *args, stream())
     else:
         call("mk_gather_backproject_kf", *args, ptr(kf), kfn, stream())
@@ -1068,7 +1192,15 @@ def gather_backproject_bwd(idx, corr, gX, gY, K0, K1, B, rows_per_pair, n0, n1):
     return gk0, gd0, gk1, gd1
 
 
-def refine_pose(X, Y, Rh, th, score, B, it_matches, it_ransac, th_inlier, num_ref, min_inliers, invalid=None):
+def pose_finalize(R, t, conf, invalid):
+    """mk_pose_finalize: the batch-level invalid rule -- every pose of R [B, 3, 3], t [B, 1, 3], conf [B, 1] is zeroed in place
+    when the word `invalid` is set."""
+    call("mk_pose_finalize", ptr(R), ptr(t), ptr(conf), ptr(invalid), R.shape[0], stream())
+
+
+def refine_pose(X, Y, Rh, th, score, B, it_matches, it_ransac, th_inlier, num_ref, min_inliers, invalid=None, finalize=True):
+    """finalize=False leaves mk_pose_finalize to the caller (a forward that solves its pairs in chunks applies the batch-level
+    invalid rule once, over all of them: pose_finalize)."""
     X, Y, Rh, th, score = _c(X, Y, Rh, th, score)
     k = X.shape[1]
     dev = X.device
@@ -1082,5 +1214,6 @@ def refine_pose(X, Y, Rh, th, score, B, it_matches, it_ransac, th_inlier, num_re
         invalid = torch.zeros((1,), device=dev, dtype=torch.int32)
     call("mk_refine_pose", ptr(X), ptr(Y), ptr(Rh), ptr(th), ptr(score), float(th_inlier), int(num_ref), int(min_inliers),
          ptr(R), ptr(t), ptr(conf), ptr(best), ptr(mask), ptr(rounds), ptr(invalid), B, it_matches, it_ransac, k, stream())
-    call("mk_pose_finalize", ptr(R), ptr(t), ptr(conf), ptr(invalid), B, stream())
+    if finalize:
+        call("mk_pose_finalize", ptr(R), ptr(t), ptr(conf), ptr(invalid), B, stream())
     return R, t, conf, best, mask, rounds, invalid

@@ -308,20 +308,36 @@ def heads_forward(W, ws, feat, nimg, gh, gw, cfg):
                           down=float(mk["DINOV2"]["DOWN_FACTOR"]))
 
 
-def match(W, cfg, dsc0, dsc1, scr0, scr1, lean=False, keyframe_index=None):
-    """keyframe_index (keyframe mode): int32 device map pair -> row of dsc0 / scr0 (which then hold the K keyframes)."""
+def match_uses_split(cfg, C):
+    """Does match() take the split-fp16 correlation for C-channel descriptors under this configuration?  AMD.MATCHER_CORR:
+    'auto' = the split-fp16 correlation on the 16-bit matrix cores when its preconditions hold (L2-normalised 128-channel
+    descriptors, mickey_hip.h: mk_dual_softmax_split), else the exact fp32 MFMA; 'fp32' | 'split16' (ValueError without them)."""
+    fm = cfg["FEATURE_MATCHER"]
+    if fm["TYPE"] != "DualSoftmax":
+        return False
+    mode = str(cfg["AMD"].get("MATCHER_CORR", "auto")).lower()
+    can = bool(cfg["MICKEY"]["DSC_HEAD"]["NORM_DSC"]) and ops.dual_softmax_split_ok(C, float(fm["DUAL_SOFTMAX"]["TEMPERATURE"]))
+    if mode == "split16" and not can:
+        raise ValueError("AMD.MATCHER_CORR: split16 needs MICKEY.DSC_HEAD.NORM_DSC, 128 descriptor channels and T >= 0.0145")
+    return can and mode != "fp32"
+
+
+def match(W, cfg, dsc0, dsc1, scr0, scr1, lean=False, keyframe_index=None, pair_index=None, planes=None, out=None):
+    """keyframe_index (keyframe mode): int32 device map pair -> row of dsc0 / scr0 (which then hold the K keyframes).
+    pair_index (pair-list mode): the (idx0, idx1) device maps of a chunk of pairs into the image sets dsc0 / scr0 and dsc1 / scr1
+    (ops._pair_arg); planes: the sets' split planes, made once per forward (ops.dsc_split_planes; only where match_uses_split);
+    out: the chunk's (scores, kp_scores, final_scores) buffers (ops._outs)."""
     fm = cfg["FEATURE_MATCHER"]
     kf = {} if keyframe_index is None else {"keyframe_index": keyframe_index}   # (the standard call keeps its exact signature)
+    if pair_index is not None:
+        kf = {"pair_index": pair_index, "out": out}
+        if planes is not None:
+            kf["planes"] = planes
     if fm["TYPE"] == "DualSoftmax":
         ds = fm["DUAL_SOFTMAX"]
-        # AMD.MATCHER_CORR: 'auto' = the split-fp16 correlation on the 16-bit matrix cores when its preconditions hold
-        # (L2-normalised 128-channel descriptors, mickey_hip.h: mk_dual_softmax_split), else the exact fp32 MFMA; 'fp32' | 'split16'
-        mode = str(cfg["AMD"].get("MATCHER_CORR", "auto")).lower()
-        can = bool(cfg["MICKEY"]["DSC_HEAD"]["NORM_DSC"]) and ops.dual_softmax_split_ok(dsc0.shape[1], float(ds["TEMPERATURE"]))
-        if mode == "split16" and not can:
-            raise ValueError("AMD.MATCHER_CORR: split16 needs MICKEY.DSC_HEAD.NORM_DSC, 128 descriptor channels and T >= 0.0145")
         return ops.dual_softmax(dsc0, dsc1, scr0, scr1, float(ds["TEMPERATURE"]), W.dustbin if ds["USE_DUSTBIN"] else None,
-                                want_scores=not lean, want_kp=not lean, want_final=True, split=can and mode != "fp32", **kf)
+                                want_scores=not lean, want_kp=not lean, want_final=True, split=match_uses_split(cfg, dsc0.shape[1]),
+                                **kf)
     if fm["TYPE"] == "Sinkhorn":
         # the reference's Sinkhorn branch is unreachable through featureMatcher.forward (SURVEY D4); the maths
         # restated is feature_matcher.py:125-137 with matching_mat(dsc0, dsc1, None)
@@ -332,18 +348,23 @@ def match(W, cfg, dsc0, dsc1, scr0, scr1, lean=False, keyframe_index=None):
 
 
 def solve(cfg, final_scores, kps0, depth0, kps1, depth1, K0, K1, seed=0, offset=0, noise_outer=None, noise_inner=None,
-          idx3_in=None, debug=False, offset_dev=None, pair_base=0, ws=None, keyframe_index=None):
+          idx3_in=None, debug=False, offset_dev=None, pair_base=0, ws=None, keyframe_index=None, pair_index=None, invalid=None,
+          finalize=True):
     """reference probabilisticProcrustes.py:183-348 on device.  Returns a dict with R [B,3,3], t [B,1,3],
     inliers [B,1] and the intermediates needed for the inlier list.  pair_base = global index of pair 0 (keys the
     Philox streams: sharding a batch over calls / GPUs does not change any pair's draws).  keyframe_index (keyframe mode):
-    int32 device map pair -> row of kps0 / depth0 (which then hold the K keyframes); K0 stays per pair."""
+    int32 device map pair -> row of kps0 / depth0 (which then hold the K keyframes); K0 stays per pair.  pair_index (pair-list
+    mode): the (idx0, idx1) device maps of these pairs into the image sets kps0 / depth0 and kps1 / depth1; K0 / K1 stay per pair.
+    invalid / finalize=False: a forward that solves its pairs in chunks hands every chunk the ONE invalid word of the forward and
+    applies the batch-level rule itself, once (ops.pose_finalize)."""
     P = cfg["PROCRUSTES"]
     it_m, it_r, ns, k3 = int(P["IT_MATCHES"]), int(P["IT_RANSAC"]), int(P["NUM_SAMPLED_MATCHES"]), int(P["NUM_CORR_3D_3D"])
     if k3 != 3:
         raise ValueError("NUM_CORR_3D_3D must be 3 (the inference solver fits minimal 3-point samples)")
     B, n0, n1 = final_scores.shape
     dev = final_scores.device
-    invalid = torch.zeros((1,), device=dev, dtype=torch.int32)
+    if invalid is None:
+        invalid = torch.zeros((1,), device=dev, dtype=torch.int32)
     # the sampler's workspace lives in the model's Workspace (ws) like every other buffer of a forward: zeroed once, self-cleaning
     # afterwards (mickey_hip.h); one model is one forward at a time
     work = None
@@ -355,12 +376,14 @@ def solve(cfg, final_scores, kps0, depth0, kps1, depth1, K0, K1, seed=0, offset=
     idx, cnt = ops.exprace_topk(final_scores.reshape(B, n0 * n1), it_m, ns, noise=noise_outer, seed=seed, offset=offset,
                                 invalid=invalid, offset_dev=offset_dev, pair_base=pair_base, work=work)
     X, Y, w, corr = ops.gather_backproject(idx, final_scores, kps0, depth0, kps1, depth1, K0, K1, it_m,
-                                           **({} if keyframe_index is None else {"keyframe_index": keyframe_index}))
+                                           **({} if keyframe_index is None else {"keyframe_index": keyframe_index}),
+                                           **({} if pair_index is None else {"pair_index": pair_index}))
     Rh, th, score, idx3 = ops.ransac_hypotheses(X, Y, w, it_r, float(P["TH_SOFT_INLIER"]), noise3=noise_inner,
                                                 idx3_in=idx3_in, seed=seed, offset=offset + 1, offset_dev=offset_dev,
                                                 set_base=pair_base * it_m)
     R, t, conf, best, mask, rounds, invalid = ops.refine_pose(X, Y, Rh, th, score, B, it_m, it_r, float(P["TH_INLIER"]),
-                                                              int(P["NUM_REFINEMENTS"]), k3, invalid=invalid)
+                                                              int(P["NUM_REFINEMENTS"]), k3, invalid=invalid,
+                                                              **({} if finalize else {"finalize": False}))
     out = {"R": R, "t": t, "inliers": conf, "best": best, "mask": mask, "corr": corr, "weights": w, "invalid": invalid,
            "it_ransac": it_r, "it_matches": it_m}
     if debug:
