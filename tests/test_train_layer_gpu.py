@@ -160,7 +160,8 @@ def _hip(tl, x, src, w, go, need_x=True, need_w=True):
 
 
 # ---- 1: the whole layer ------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("N,L,S", [(1, 1, None), (2, 37, 29), (3, 200, None), (1, 130, 333)])
+@pytest.mark.parametrize("N,L,S", [(1, 1, None), (2, 37, 29), (3, 200, None), (1, 130, 333),
+                                   (1, 65, None), (2, 129, 63), (1, 64, 128)])   # L, S at the edges of the 64-token chunks
 def test_layer_parity_per_shape(tl, N, L, S):
     seed, ins, ref, t32 = _case(tl, N, L, S)
     got = _hip(tl, *ins)
