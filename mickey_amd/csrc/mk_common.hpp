@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "../../include/mickey_hip.h"
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
@@ -78,6 +80,17 @@ struct RowMaps {
   int N1;
   int mode() const { return idx1 ? MAP_PAIRS : idx0 ? MAP_KF : MAP_NONE; }
 };
+// The one place where rm.mode() becomes a template argument: f(std::integral_constant<int, MAP_...>{}) -> whatever f returns.
+//   with_row_map(rm, [&](auto M) { return impl<decltype(M)::value>(..., rm, st); });
+// (MAP_NONE / MAP_KF are the instantiations of the plain and the _kf call: the same kernels, the same bits.)
+template <typename F>
+inline auto with_row_map(const RowMaps& rm, F&& f) {
+  switch (rm.mode()) {
+    case MAP_NONE: return f(std::integral_constant<int, MAP_NONE>{});
+    case MAP_KF: return f(std::integral_constant<int, MAP_KF>{});
+    default: return f(std::integral_constant<int, MAP_PAIRS>{});
+  }
+}
 inline int check_row_maps(const char* who, const RowMaps& m, int B) {
   MK_CHECK_ARG(m.idx0 ? m.N0 > 0 : m.N0 == B, "%s: need N0 > 0 with a map on operand 0, N0 == B without", who);
   MK_CHECK_ARG(m.idx1 ? m.N1 > 0 : m.N1 == B, "%s: need N1 > 0 with a map on operand 1, N1 == B without", who);

@@ -671,7 +671,8 @@ long long mk_dual_softmax_work_floats(int B, int n0, int n1, int own_copy) {
 
 }  // extern "C"
 
-// the exact-fp32 dual softmax; MAP / rm: the operand maps (mk_common.hpp: pair_rows; mickey_hip.h: mk_dual_softmax_kf, _pairs).
+// the exact-fp32 dual softmax; MAP / rm: the operand maps (mk_common.hpp: pair_rows; mickey_hip.h: mk_dual_softmax_kf, _pairs) -- MAP
+// is chosen from rm by the entry point, through with_row_map (mk_common.hpp), as for every *_impl / split_passes below.
 // lse_out (training forward, mk::ds::dual_softmax_train_fwd): the merged log2-sums go there instead of `work`, merged with the
 // dustbin read from the device pointer dustbin_dev (use_dustbin / dustbin unused)
 template <int MAP>
@@ -747,18 +748,10 @@ int mk_dual_softmax_pairs(const float* dsc0, const float* dsc1, const float* scr
   MK_CHECK_ARG(dsc0 && dsc1 && work, "mk_dual_softmax_pairs: null pointer");
   const RowMaps rm{idx0, N0, idx1, N1};
   if (const int rc = check_row_maps("mk_dual_softmax_pairs", rm, B)) return rc;
-  hipStream_t st = (hipStream_t)stream;
-  switch (rm.mode()) {   // (the instantiations of the plain and the _kf call: the same kernels, the same bits)
-    case MAP_NONE:
-      return dual_softmax_impl<MAP_NONE>(dsc0, dsc1, scr0, scr1, inv_temperature, use_dustbin, dustbin, scores, kp_scores, final_scores,
-                                         work, B, C, n0, n1, rm, st);
-    case MAP_KF:
-      return dual_softmax_impl<MAP_KF>(dsc0, dsc1, scr0, scr1, inv_temperature, use_dustbin, dustbin, scores, kp_scores, final_scores,
-                                       work, B, C, n0, n1, rm, st);
-    default:
-      return dual_softmax_impl<MAP_PAIRS>(dsc0, dsc1, scr0, scr1, inv_temperature, use_dustbin, dustbin, scores, kp_scores,
-                                          final_scores, work, B, C, n0, n1, rm, st);
-  }
+  return with_row_map(rm, [&](auto M) {
+    return dual_softmax_impl<decltype(M)::value>(dsc0, dsc1, scr0, scr1, inv_temperature, use_dustbin, dustbin, scores, kp_scores,
+                                                 final_scores, work, B, C, n0, n1, rm, (hipStream_t)stream);
+  });
 }
 
 // row / column partials + log2-sum-exp vectors of B pairs (the part of the split path's work that is per pair)
@@ -801,7 +794,7 @@ static int split_check_args(float* work, int B, int C, int n0, int n1, const flo
 template <int MAP>
 static int split_passes(const uint4* P0, const uint4* P1, const float* scr0, const float* scr1, float inv_temperature, int use_dustbin,
                         float dustbin, float* scores, float* kp_scores, float* final_scores, float* pass_work, int B, int n0, int n1,
-                        const RowMaps& rm, hipStream_t st, float* lse_out, const float* dustbin_dev) {
+                        const RowMaps& rm, hipStream_t st, float* lse_out = nullptr, const float* dustbin_dev = nullptr) {
   const float LOG2E = 1.4426950408889634f;
   const int nmax = n0 > n1 ? n0 : n1, nrb = (n0 + RT - 1) / RT, ntb = (n1 + RT - 1) / RT;
   float* partr = pass_work;
@@ -841,23 +834,6 @@ static int split_passes(const uint4* P0, const uint4* P1, const float* scr0, con
   return MK_OK;
 }
 
-static int split_passes_any(const uint4* P0, const uint4* P1, const float* scr0, const float* scr1, float inv_temperature,
-                            int use_dustbin, float dustbin, float* scores, float* kp_scores, float* final_scores, float* pass_work, int B,
-                            int n0, int n1, const RowMaps& rm, hipStream_t st, float* lse_out = nullptr,
-                            const float* dustbin_dev = nullptr) {
-  switch (rm.mode()) {   // (MAP_NONE / MAP_KF: the instantiations of the plain and the _kf call -- the same kernels, the same bits)
-    case MAP_NONE:
-      return split_passes<MAP_NONE>(P0, P1, scr0, scr1, inv_temperature, use_dustbin, dustbin, scores, kp_scores, final_scores, pass_work,
-                                    B, n0, n1, rm, st, lse_out, dustbin_dev);
-    case MAP_KF:
-      return split_passes<MAP_KF>(P0, P1, scr0, scr1, inv_temperature, use_dustbin, dustbin, scores, kp_scores, final_scores, pass_work, B,
-                                  n0, n1, rm, st, lse_out, dustbin_dev);
-    default:
-      return split_passes<MAP_PAIRS>(P0, P1, scr0, scr1, inv_temperature, use_dustbin, dustbin, scores, kp_scores, final_scores, pass_work,
-                                     B, n0, n1, rm, st, lse_out, dustbin_dev);
-  }
-}
-
 // the split-fp16 dual softmax from fp32 descriptors: planes first (of the rm.N0 / rm.N1 images of each operand, ONCE each), then
 // the passes.  work: [planes of operand 0: rows0 images reserved | planes of operand 1 | pass work]; shared: both operands are one
 // image set whose planes are made once and read by both sides (P1 = P0, no second region)
@@ -873,8 +849,10 @@ static int dual_softmax_split_fwd(const float* dsc0, const float* dsc1, const fl
   hipLaunchKernelGGL(dsc_split_kernel, dim3(nrb, rm.N0), dim3(512), 0, st, dsc0, P0, n0, nrb);
   if (!shared) hipLaunchKernelGGL(dsc_split_kernel, dim3(ntb, rm.N1), dim3(512), 0, st, dsc1, P1, n1, ntb);
   MK_CHECK_LAUNCH();
-  return split_passes_any(P0, P1, scr0, scr1, inv_temperature, use_dustbin, dustbin, scores, kp_scores, final_scores, pass_work, B, n0,
-                          n1, rm, st, lse_out, dustbin_dev);
+  return with_row_map(rm, [&](auto M) {
+    return split_passes<decltype(M)::value>(P0, P1, scr0, scr1, inv_temperature, use_dustbin, dustbin, scores, kp_scores, final_scores,
+                                            pass_work, B, n0, n1, rm, st, lse_out, dustbin_dev);
+  });
 }
 
 extern "C" {
@@ -923,8 +901,10 @@ int mk_dual_softmax_split_planes(const float* planes0, const float* planes1, con
   const RowMaps rm{idx0, N0, idx1, N1};
   if (const int rc = check_row_maps("mk_dual_softmax_split_planes", rm, B)) return rc;
   if (const int rc = split_check_args(work, B, 16 * SP_KS, n0, n1, scr0, scr1, inv_temperature, kp_scores, final_scores)) return rc;
-  return split_passes_any((const uint4*)planes0, (const uint4*)planes1, scr0, scr1, inv_temperature, use_dustbin, dustbin, scores,
-                          kp_scores, final_scores, work, B, n0, n1, rm, (hipStream_t)stream);
+  return with_row_map(rm, [&](auto M) {
+    return split_passes<decltype(M)::value>((const uint4*)planes0, (const uint4*)planes1, scr0, scr1, inv_temperature, use_dustbin,
+                                            dustbin, scores, kp_scores, final_scores, work, B, n0, n1, rm, (hipStream_t)stream);
+  });
 }
 
 }  // extern "C"
@@ -1024,15 +1004,10 @@ int mk_sinkhorn_pairs(const float* dsc0, const float* dsc1, const float* scr0, c
   MK_CHECK_ARG(dsc0 && dsc1 && work && (scores || final_scores), "mk_sinkhorn_pairs: null pointer");
   const RowMaps rm{idx0, N0, idx1, N1};
   if (const int rc = check_row_maps("mk_sinkhorn_pairs", rm, B)) return rc;
-  hipStream_t st = (hipStream_t)stream;
-  switch (rm.mode()) {
-    case MAP_NONE:
-      return sinkhorn_impl<MAP_NONE>(dsc0, dsc1, scr0, scr1, alpha, iters, scores, kp_scores, final_scores, work, B, C, n0, n1, rm, st);
-    case MAP_KF:
-      return sinkhorn_impl<MAP_KF>(dsc0, dsc1, scr0, scr1, alpha, iters, scores, kp_scores, final_scores, work, B, C, n0, n1, rm, st);
-    default:
-      return sinkhorn_impl<MAP_PAIRS>(dsc0, dsc1, scr0, scr1, alpha, iters, scores, kp_scores, final_scores, work, B, C, n0, n1, rm, st);
-  }
+  return with_row_map(rm, [&](auto M) {
+    return sinkhorn_impl<decltype(M)::value>(dsc0, dsc1, scr0, scr1, alpha, iters, scores, kp_scores, final_scores, work, B, C, n0, n1, rm,
+                                             (hipStream_t)stream);
+  });
 }
 
 int mk_mutual_nn(const float* scores, int* matches, int* count, int* work, int B, int n0, int n1, mk_stream_t stream) {

@@ -39,7 +39,7 @@ __device__ __forceinline__ void inv3(const float* K, float* o) {
 }
 
 // MAP (mk_common.hpp: pair_rows): pair b reads row b0 of kps0 / dep0 and row b1 of kps1 / dep1 (keyframe mode: operand 0 through
-// idx0; pair-list mode: a map on each side); K0 / K1 stay per pair
+// idx0; pair-list mode: a map on each side; chosen on the host by with_row_map, mk_common.hpp); K0 / K1 stay per pair
 template <int MAP>
 __global__ __launch_bounds__(256) void gather_backproject_kernel(const int* __restrict__ idx, const float* __restrict__ fs,
                                                                  const float* __restrict__ kps0, const float* __restrict__ dep0,
@@ -610,19 +610,10 @@ int mk_gather_backproject_pairs(const int* idx, const float* final_scores, const
   if (const int rc = check_row_maps("mk_gather_backproject_pairs", rm, B)) return rc;
   const dim3 g((k + 255) / 256, B * rows_per_pair);
   hipStream_t st = (hipStream_t)stream;
-  switch (rm.mode()) {   // (MAP_NONE / MAP_KF: the instantiations of the plain and the _kf call)
-    case MAP_NONE:
-      hipLaunchKernelGGL(gather_backproject_kernel<MAP_NONE>, g, dim3(256), 0, st, idx, final_scores, kps0, depth0, kps1, depth1, K0, K1,
-                         X, Y, wts, corr, rows_per_pair, k, n0, n1, idx0, N0, idx1, N1);
-      break;
-    case MAP_KF:
-      hipLaunchKernelGGL(gather_backproject_kernel<MAP_KF>, g, dim3(256), 0, st, idx, final_scores, kps0, depth0, kps1, depth1, K0, K1, X,
-                         Y, wts, corr, rows_per_pair, k, n0, n1, idx0, N0, idx1, N1);
-      break;
-    default:
-      hipLaunchKernelGGL(gather_backproject_kernel<MAP_PAIRS>, g, dim3(256), 0, st, idx, final_scores, kps0, depth0, kps1, depth1, K0, K1,
-                         X, Y, wts, corr, rows_per_pair, k, n0, n1, idx0, N0, idx1, N1);
-  }
+  with_row_map(rm, [&](auto M) {
+    hipLaunchKernelGGL(gather_backproject_kernel<decltype(M)::value>, g, dim3(256), 0, st, idx, final_scores, kps0, depth0, kps1, depth1,
+                       K0, K1, X, Y, wts, corr, rows_per_pair, k, n0, n1, idx0, N0, idx1, N1);
+  });
   MK_CHECK_LAUNCH();
   return MK_OK;
 }

@@ -258,6 +258,24 @@ class MickeyRelativePose(nn.Module):
         return self._dev_weights
 
     # ---- forward ---------------------------------------------------------------------------------
+    def _images(self, t):   # -> fp32 device tensor with a dense last dimension (the patch kernel takes any outer strides)
+        t = t.to(device=self._anchor.device, dtype=torch.float32)
+        return t if t.stride(3) == 1 else t.contiguous()
+
+    def _arm_sat_flag(self):
+        """Split-operand heads hold activations as x * 64 = hi + lo in fp16: a value beyond +-1023 is clamped.  The plane-writing
+        kernels report it (and any NaN) into this word of the model's own workspace, never silently (split_saturated() reads it)."""
+        if self.heads_split and self._sat_flag is None:
+            self._sat_flag = torch.zeros((1,), device=self._anchor.device, dtype=torch.int32)
+        self._ws.sat_flag = self._sat_flag if self.heads_split else None
+
+    def _next_call(self):   # one call number per forward: its Philox stream offset = 2 * (forwards so far), kept on the device
+        from . import ops
+        if self._ctr is None:
+            self._ctr = torch.full((1,), 2 * self._calls, device=self._anchor.device, dtype=torch.int64)
+        self._calls += 1
+        ops.counter_add(self._ctr, 2)
+
     def _keyframe_map(self, data):
         """Keyframe mode (data["keyframe_index"]): validate the pair -> keyframe map on the host (ValueError: wrong length, not
         integers, out of [0, K)) and return the model's device int32 copy of it (workspace).  A map given as a device tensor is
@@ -280,23 +298,16 @@ class MickeyRelativePose(nn.Module):
             _kf = self._keyframe_map(data)   # validated before anything is launched
         W = self.device_weights()
         dev = self._anchor.device
-        im0 = data["image0"].to(device=dev, dtype=torch.float32)
-        im1 = data["image1"].to(device=dev, dtype=torch.float32)
+        im0, im1 = self._images(data["image0"]), self._images(data["image1"])
         B = im0.shape[0]
         same = im0.shape == im1.shape
         if _kf is not None:   # K keyframes + B queries: one pass over K + B images when the frame sizes agree
             same = im0.shape[1:] == im1.shape[1:]
         rows = (B, B) if _kf is None else (B, im1.shape[0])   # rows of the image-0 / image-1 outputs
         # one 2B-image pass when shapes agree (the two image sets are patched into one token matrix: no copy of the images)
-        im0, im1 = (t if t.stride(3) == 1 else t.contiguous() for t in (im0, im1))   # the patch kernel takes any outer strides
         imgs = [(im0, im1)] if same else [(im0,), (im1,)]
         outs = []
-        if self.heads_split and self._sat_flag is None:
-            # split-operand heads hold activations as x * 64 = hi + lo in fp16: a value beyond +-1023 is clamped.  The kernels
-            # report it (and any NaN) into this word, passed to every plane-writing call through the model's own workspace --
-            # per model, never process-wide (split_saturated() reads it): never silently
-            self._sat_flag = torch.zeros((1,), device=dev, dtype=torch.int32)
-        self._ws.sat_flag = self._sat_flag if self.heads_split else None
+        self._arm_sat_flag()
         for im in imgs:
             feat, gh, gw = pipeline.encoder_forward(W, self._ws, im)
             scr, kps, depth, dsc = pipeline.heads_forward(W, self._ws, feat, sum(t.shape[0] for t in im), gh, gw, self.cfg)
@@ -339,12 +350,7 @@ class MickeyRelativePose(nn.Module):
         dev = self._anchor.device
         K0 = data["K_color0"].to(device=dev, dtype=torch.float32).contiguous()
         K1 = data["K_color1"].to(device=dev, dtype=torch.float32).contiguous()
-        # offset of this call's Philox streams = 2 * (number of forwards so far), kept on the device
-        if self._ctr is None:
-            self._ctr = torch.full((1,), 2 * self._calls, device=dev, dtype=torch.int64)
-        from . import ops
-        self._calls += 1
-        ops.counter_add(self._ctr, 2)
+        self._next_call()
         # data["pair_base"] (optional, int): global index of this batch's first pair -- a rank of a sharded batch passes its
         # shard offset so that the poses do not depend on the sharding (mickey_amd.distributed.shard_batch sets it)
         sol = pipeline.solve(self.cfg, data["final_scores"], data["kps0"], data["depth_kp0"], data["kps1"], data["depth_kp1"],
@@ -393,13 +399,10 @@ class MickeyRelativePose(nn.Module):
         dev, amd = self._anchor.device, self.cfg["AMD"]
         ichunk, pchunk = max(1, int(amd.get("IMAGE_CHUNK", 64))), max(1, int(amd.get("PAIR_CHUNK", 32)))
         keep = bool(amd.get("PAIRLIST_SCORES", False))
-        images = data["images"].to(device=dev, dtype=torch.float32)
-        images = images if images.stride(3) == 1 else images.contiguous()
+        images = self._images(data["images"])
         K = data["K_color"].to(device=dev, dtype=torch.float32).contiguous()
         maps = torch.from_numpy(np.ascontiguousarray(host.T)).to(dev)   # [2, P]: the two maps of the *_pairs entry points
-        if self.heads_split and self._sat_flag is None:   # (see compute_correspondences)
-            self._sat_flag = torch.zeros((1,), device=dev, dtype=torch.int32)
-        self._ws.sat_flag = self._sat_flag if self.heads_split else None
+        self._arm_sat_flag()
         parts = []
         for lo in range(0, N, ichunk):
             im = images[lo:lo + ichunk]
@@ -423,10 +426,7 @@ class MickeyRelativePose(nn.Module):
             full = [torch.empty((P, n, n), device=dev, dtype=torch.float32) if w else None for w in wants]
         else:
             full = [self._ws.get("pairlist_" + nm, (min(pchunk, P), n, n), torch.float32, dev) if w else None for nm, w in zip(names, wants)]
-        if self._ctr is None:
-            self._ctr = torch.full((1,), 2 * self._calls, device=dev, dtype=torch.int64)
-        self._calls += 1
-        ops.counter_add(self._ctr, 2)   # ONE call number for the forward, as one standard forward over the P pairs takes
+        self._next_call()   # ONE call number for the forward, as one standard forward over the P pairs takes
         invalid = torch.zeros((1,), device=dev, dtype=torch.int32)
         pair_base = int(data.get("pair_base", 0))
         sols = []

@@ -842,6 +842,26 @@ def _one_mode(keyframe_index, pair_index):
         raise ValueError("keyframe_index and pair_index are mutually exclusive")
 
 
+def _row_maps(keyframe_index, pair_index, rows0, rows1, dev, P=None):
+    """The calling mode of a matcher / solver wrapper (plain, keyframe_index= or pair_index=; rows0 / rows1: the rows operand 0 /
+    operand 1 hold; P: the pair count where the caller knows it) -> (suffix, maps, rows, P), with which the wrapper finishes the
+    call without looking at the mode again: the entry point is the plain name + suffix, its trailing arguments are
+    *map(ptr, maps), *rows, and P is the pair count.
+        plain      "",        (),           (),             P = rows1
+        keyframe   "_kf",     (map,),       (K,),           P = rows1                       (_kf_arg)
+        pair list  "_pairs",  (idx0, idx1), (rows0, rows1), P = the maps' / the list's length (_pair_arg)
+    The maps come back as tensors: they must live until the call is enqueued."""
+    _one_mode(keyframe_index, pair_index)
+    if pair_index is not None:
+        i0, i1, P = _pair_arg(pair_index, rows0, rows1, dev, P)
+        return "_pairs", (i0, i1), (rows0, rows1), P
+    P = rows1 if P is None else P
+    if keyframe_index is not None:
+        kf, K = _kf_arg(keyframe_index, P, rows0, dev)
+        return "_kf", (kf,), (K,), P
+    return "", (), (), P
+
+
 def _outs(out, shape, wants, dev):
     """The three [B, n0, n1] outputs of a matcher: fresh, or the caller's (out = (scores, kp_scores, final_scores), an entry
     None where not wanted: a chunked caller writes every chunk into its own buffers)."""
@@ -864,6 +884,18 @@ def dsc_split_planes(dsc):
     return planes
 
 
+# dual_softmax: (split, planes given, entry-point suffix of the mode) -> (work-size query, entry point)
+_DUAL_SOFTMAX = {
+    (False, False, ""): ("mk_dual_softmax_work_floats", "mk_dual_softmax"),
+    (False, False, "_kf"): ("mk_dual_softmax_work_floats", "mk_dual_softmax_kf"),
+    (False, False, "_pairs"): ("mk_dual_softmax_work_floats", "mk_dual_softmax_pairs"),
+    (True, False, ""): ("mk_dual_softmax_split_work_floats", "mk_dual_softmax_split"),
+    (True, False, "_kf"): ("mk_dual_softmax_split_work_floats", "mk_dual_softmax_split_kf"),
+    (True, False, "_pairs"): ("mk_dual_softmax_split_pairs_work_floats", "mk_dual_softmax_split_pairs"),
+    (True, True, "_pairs"): ("mk_dual_softmax_split_planes_work_floats", "mk_dual_softmax_split_planes"),
+}
+
+
 def dual_softmax(dsc0, dsc1, scr0=None, scr1=None, temperature=0.1, dustbin=None, want_scores=True, want_kp=True,
                  want_final=True, split=False, keyframe_index=None, pair_index=None, planes=None, out=None):
     """Returns (scores, kp_scores, final_scores) (None where not requested).  split: the correlation on the 16-bit matrix
@@ -880,51 +912,22 @@ def dual_softmax(dsc0, dsc1, scr0=None, scr1=None, temperature=0.1, dustbin=None
     K, C, n0 = dsc0.shape
     B, n1 = dsc1.shape[0], dsc1.shape[2]
     dev = dsc0.device
-    if pair_index is not None:
-        i0, i1, P = _pair_arg(pair_index, K, B, dev)
-        scores, kp, fin = _outs(out, (P, n0, n1), (want_scores, want_kp and scr0 is not None, want_final and scr0 is not None), dev)
-        args = (ptr(scr0), ptr(scr1), 1.0 / float(temperature), int(dustbin is not None), float(dustbin) if dustbin is not None else 0.0,
-                ptr(scores), ptr(kp), ptr(fin))
-        maps = (ptr(i0), ptr(i1), K, B, stream())
-        if split and planes is not None:
-            work = torch.empty((query("mk_dual_softmax_split_planes_work_floats", P, n0, n1),), device=dev, dtype=torch.float32)
-            call("mk_dual_softmax_split_planes", ptr(planes[0]), ptr(planes[1]), *args, ptr(work), P, n0, n1, *maps)
-        elif split:
-            shared = dsc0.data_ptr() == dsc1.data_ptr() and n0 == n1 and K == B
-            work = torch.empty((query("mk_dual_softmax_split_pairs_work_floats", P, n0, n1, K, B, int(shared)),), device=dev,
-                               dtype=torch.float32)
-            call("mk_dual_softmax_split_pairs", ptr(dsc0), ptr(dsc1), *args, ptr(work), P, C, n0, n1, *maps)
-        else:
-            work = torch.empty((query("mk_dual_softmax_work_floats", P, n0, n1, int(scores is None and fin is None)),), device=dev,
-                               dtype=torch.float32)
-            call("mk_dual_softmax_pairs", ptr(dsc0), ptr(dsc1), *args, ptr(work), P, C, n0, n1, *maps)
-        return scores, kp, fin
-    if planes is not None or out is not None:
-        raise ValueError("planes= and out= belong to pair-list mode (pair_index=)")
-    if keyframe_index is None:
-        assert K == B, "dsc0 and dsc1 hold different batch counts (keyframe mode needs keyframe_index)"
-    kf, kfn = _kf_arg(keyframe_index, B, K, dev)
-    mk = lambda want: torch.empty((B, n0, n1), device=dev, dtype=torch.float32) if want else None  # noqa: E731
-    scores = mk(want_scores)
-    kp = mk(want_kp and scr0 is not None)
-    fin = mk(want_final and scr0 is not None)
-    if split:
-        work = torch.empty((query("mk_dual_softmax_split_work_floats", B, n0, n1),), device=dev, dtype=torch.float32)
-        args = (ptr(dsc0), ptr(dsc1), ptr(scr0), ptr(scr1), 1.0 / float(temperature), int(dustbin is not None),
-                float(dustbin) if dustbin is not None else 0.0, ptr(scores), ptr(kp), ptr(fin), ptr(work), B, C, n0, n1)
-        if kf is None:
-            call("mk_dual_softmax_split", *args, stream())
-        else:
-            call("mk_dual_softmax_split_kf", *args, ptr(kf), kfn, stream())
-        return scores, kp, fin
-    work = torch.empty((query("mk_dual_softmax_work_floats", B, n0, n1, int(scores is None and fin is None)),), device=dev,
-                       dtype=torch.float32)
-    args = (ptr(dsc0), ptr(dsc1), ptr(scr0), ptr(scr1), 1.0 / float(temperature), int(dustbin is not None),
-            float(dustbin) if dustbin is not None else 0.0, ptr(scores), ptr(kp), ptr(fin), ptr(work), B, C, n0, n1)
-    if kf is None:
-        call("mk_dual_softmax", *args, stream())
-    else:
-        call("mk_dual_softmax_kf", *args, ptr(kf), kfn, stream())
+    if pair_index is None:
+        if planes is not None or out is not None:
+            raise ValueError("planes= and out= belong to pair-list mode (pair_index=)")
+        if keyframe_index is None:
+            assert K == B, "dsc0 and dsc1 hold different batch counts (keyframe mode needs keyframe_index)"
+    suffix, maps, rows, P = _row_maps(keyframe_index, pair_index, K, B, dev)
+    scores, kp, fin = _outs(out, (P, n0, n1), (want_scores, want_kp and scr0 is not None, want_final and scr0 is not None), dev)
+    wq, entry = _DUAL_SOFTMAX[bool(split), bool(split) and planes is not None, suffix]
+    # what each work-size query takes after (P, n0, n1); shared: one image set on both sides, its planes are made once
+    wq_args = {"mk_dual_softmax_work_floats": (int(scores is None and fin is None),),
+               "mk_dual_softmax_split_pairs_work_floats": (K, B, int(dsc0.data_ptr() == dsc1.data_ptr() and n0 == n1 and K == B))}
+    work = torch.empty((query(wq, P, n0, n1, *wq_args.get(wq, ())),), device=dev, dtype=torch.float32)
+    # (the passes on ready planes take the planes for the descriptors, and no channel count)
+    lead, dims = ((planes[0], planes[1]), (P, n0, n1)) if entry == "mk_dual_softmax_split_planes" else ((dsc0, dsc1), (P, C, n0, n1))
+    call(entry, ptr(lead[0]), ptr(lead[1]), ptr(scr0), ptr(scr1), 1.0 / float(temperature), int(dustbin is not None),
+         float(dustbin) if dustbin is not None else 0.0, ptr(scores), ptr(kp), ptr(fin), ptr(work), *dims, *map(ptr, maps), *rows, stream())
     return scores, kp, fin
 
 
@@ -966,27 +969,17 @@ def sinkhorn(dsc0, dsc1, alpha, iters=10, scr0=None, scr1=None, want_scores=True
     K, C, n0 = dsc0.shape
     B, n1 = dsc1.shape[0], dsc1.shape[2]
     dev = dsc0.device
-    if pair_index is not None:
-        i0, i1, P = _pair_arg(pair_index, K, B, dev)
-        res, kp, fin = _outs(out, (P, n0, n1), (want_scores, want_kp and scr0 is not None, want_final and scr0 is not None), dev)
-        work = torch.empty((query("mk_sinkhorn_work_floats", P, n0, n1),), device=dev, dtype=torch.float32)
-        call("mk_sinkhorn_pairs", ptr(dsc0), ptr(dsc1), ptr(scr0), ptr(scr1), float(alpha), int(iters), ptr(res), ptr(kp), ptr(fin),
-             ptr(work), P, C, n0, n1, ptr(i0), ptr(i1), K, B, stream())
-        return res if scr0 is None else (res, kp, fin)
-    if out is not None:
-        raise ValueError("out= belongs to pair-list mode (pair_index=)")
-    if keyframe_index is None:
-        assert K == B, "dsc0 and dsc1 hold different batch counts (keyframe mode needs keyframe_index)"
-    kf, kfn = _kf_arg(keyframe_index, B, K, dev)
-    mk = lambda want: torch.empty((B, n0, n1), device=dev, dtype=torch.float32) if want else None  # noqa: E731
-    out, kp, fin = mk(want_scores), mk(want_kp and scr0 is not None), mk(want_final and scr0 is not None)
-    work = torch.empty((query("mk_sinkhorn_work_floats", B, n0, n1),), device=dev, dtype=torch.float32)
-    args = (ptr(dsc0), ptr(dsc1), ptr(scr0), ptr(scr1), float(alpha), int(iters), ptr(out), ptr(kp), ptr(fin), ptr(work), B, C, n0, n1)
-    if kf is None:
-        call("mk_sinkhorn", *args, stream())
-    else:
-        call("mk_sinkhorn_kf", *args, ptr(kf), kfn, stream())
-    return out if scr0 is None else (out, kp, fin)
+    if pair_index is None:
+        if out is not None:
+            raise ValueError("out= belongs to pair-list mode (pair_index=)")
+        if keyframe_index is None:
+            assert K == B, "dsc0 and dsc1 hold different batch counts (keyframe mode needs keyframe_index)"
+    suffix, maps, rows, P = _row_maps(keyframe_index, pair_index, K, B, dev)
+    res, kp, fin = _outs(out, (P, n0, n1), (want_scores, want_kp and scr0 is not None, want_final and scr0 is not None), dev)
+    work = torch.empty((query("mk_sinkhorn_work_floats", P, n0, n1),), device=dev, dtype=torch.float32)
+    call("mk_sinkhorn" + suffix, ptr(dsc0), ptr(dsc1), ptr(scr0), ptr(scr1), float(alpha), int(iters), ptr(res), ptr(kp), ptr(fin),
+         ptr(work), P, C, n0, n1, *map(ptr, maps), *rows, stream())
+    return res if scr0 is None else (res, kp, fin)
 
 
 def mutual_nn(scores):
@@ -1066,21 +1059,13 @@ def gather_backproject(idx, final_scores, kps0, depth0, kps1, depth1, K0, K1, ro
     B, n0, n1 = final_scores.shape
     R, k = idx.shape
     dev = idx.device
-    if pair_index is not None:
-        i0, i1, _ = _pair_arg(pair_index, kps0.shape[0], kps1.shape[0], dev, P=B)
-    kf, kfn = _kf_arg(keyframe_index, B, kps0.shape[0], dev)
+    suffix, maps, rows, _ = _row_maps(keyframe_index, pair_index, kps0.shape[0], kps1.shape[0], dev, P=B)
     X = torch.empty((R, k, 3), device=dev, dtype=torch.float32)
     Y = torch.empty((R, k, 3), device=dev, dtype=torch.float32)
     wts = torch.empty((R, k), device=dev, dtype=torch.float32)
     corr = torch.empty((R, k, 6), device=dev, dtype=torch.float32)
-    args = (ptr(idx), ptr(final_scores), ptr(kps0), ptr(depth0), ptr(kps1), ptr(depth1), ptr(K0), ptr(K1), ptr(X), ptr(Y),
-            ptr(wts), ptr(corr), B, rows_per_pair, k, n0, n1)
-    if pair_index is not None:
-        call("mk_gather_backproject_pairs", *args, ptr(i0), ptr(i1), kps0.shape[0], kps1.shape[0], stream())
-    elif kf is None:
-        call("mk_gather_backproject", *args, stream())
-    else:
-        call("mk_gather_backproject_kf", *args, ptr(kf), kfn, stream())
+    call("mk_gather_backproject" + suffix, ptr(idx), ptr(final_scores), ptr(kps0), ptr(depth0), ptr(kps1), ptr(depth1), ptr(K0), ptr(K1),
+         ptr(X), ptr(Y), ptr(wts), ptr(corr), B, rows_per_pair, k, n0, n1, *map(ptr, maps), *rows, stream())
     return X, Y, wts, corr
 
 

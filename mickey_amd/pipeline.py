@@ -328,22 +328,21 @@ def match(W, cfg, dsc0, dsc1, scr0, scr1, lean=False, keyframe_index=None, pair_
     (ops._pair_arg); planes: the sets' split planes, made once per forward (ops.dsc_split_planes; only where match_uses_split);
     out: the chunk's (scores, kp_scores, final_scores) buffers (ops._outs)."""
     fm = cfg["FEATURE_MATCHER"]
-    kf = {} if keyframe_index is None else {"keyframe_index": keyframe_index}   # (the standard call keeps its exact signature)
-    if pair_index is not None:
-        kf = {"pair_index": pair_index, "out": out}
-        if planes is not None:
-            kf["planes"] = planes
     if fm["TYPE"] == "DualSoftmax":
         ds = fm["DUAL_SOFTMAX"]
+        # the mode's keywords only where set: bench.py's stage profiler wraps ops.dual_softmax with a byte count that takes the
+        # standard call's keywords and no others (the other three wrapped calls below and in solve() take any)
+        mode = {k: v for k, v in (("keyframe_index", keyframe_index), ("pair_index", pair_index), ("planes", planes), ("out", out))
+                if v is not None}
         return ops.dual_softmax(dsc0, dsc1, scr0, scr1, float(ds["TEMPERATURE"]), W.dustbin if ds["USE_DUSTBIN"] else None,
                                 want_scores=not lean, want_kp=not lean, want_final=True, split=match_uses_split(cfg, dsc0.shape[1]),
-                                **kf)
+                                **mode)
     if fm["TYPE"] == "Sinkhorn":
         # the reference's Sinkhorn branch is unreachable through featureMatcher.forward (SURVEY D4); the maths
         # restated is feature_matcher.py:125-137 with matching_mat(dsc0, dsc1, None)
         alpha = W.dustbin if W.dustbin is not None else float(fm["SINKHORN"]["DUSTBIN_SCORE_INIT"])
         return ops.sinkhorn(dsc0, dsc1, alpha, int(fm["SINKHORN"]["NUM_IT"]), scr0, scr1, want_scores=not lean,
-                            want_kp=not lean, want_final=True, **kf)
+                            want_kp=not lean, want_final=True, keyframe_index=keyframe_index, pair_index=pair_index, out=out)
     raise ValueError("feature matcher not recognized: %r" % (fm["TYPE"],))
 
 
@@ -376,14 +375,12 @@ def solve(cfg, final_scores, kps0, depth0, kps1, depth1, K0, K1, seed=0, offset=
     idx, cnt = ops.exprace_topk(final_scores.reshape(B, n0 * n1), it_m, ns, noise=noise_outer, seed=seed, offset=offset,
                                 invalid=invalid, offset_dev=offset_dev, pair_base=pair_base, work=work)
     X, Y, w, corr = ops.gather_backproject(idx, final_scores, kps0, depth0, kps1, depth1, K0, K1, it_m,
-                                           **({} if keyframe_index is None else {"keyframe_index": keyframe_index}),
-                                           **({} if pair_index is None else {"pair_index": pair_index}))
+                                           keyframe_index=keyframe_index, pair_index=pair_index)
     Rh, th, score, idx3 = ops.ransac_hypotheses(X, Y, w, it_r, float(P["TH_SOFT_INLIER"]), noise3=noise_inner,
                                                 idx3_in=idx3_in, seed=seed, offset=offset + 1, offset_dev=offset_dev,
                                                 set_base=pair_base * it_m)
     R, t, conf, best, mask, rounds, invalid = ops.refine_pose(X, Y, Rh, th, score, B, it_m, it_r, float(P["TH_INLIER"]),
-                                                              int(P["NUM_REFINEMENTS"]), k3, invalid=invalid,
-                                                              **({} if finalize else {"finalize": False}))
+                                                              int(P["NUM_REFINEMENTS"]), k3, invalid=invalid, finalize=finalize)
     out = {"R": R, "t": t, "inliers": conf, "best": best, "mask": mask, "corr": corr, "weights": w, "invalid": invalid,
            "it_ransac": it_r, "it_matches": it_m}
     if debug:
