@@ -2,148 +2,149 @@
 
 The product path calls the HIP kernels ONLY through this module; there is no CPU or ATen fallback:
 if the shared library is missing or a call fails, an exception is raised.
+
+The binding is DERIVED from the two headers at import (parse_header below): an entry point is declared in the header and
+defined in csrc/*.hip, nowhere else.  The parser is strict -- a declaration it cannot read in full raises at import.
 """
+import collections
 import ctypes
 import os
+import re
 
 import torch
 
 from . import build as _build
 
-MK_BF16, MK_F16, MK_F32 = 0, 1, 2
-ACT_NONE, ACT_RELU, ACT_GELU = 0, 1, 2
-
-_P, _I, _L, _F, _U = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_float, ctypes.c_ulonglong
-_CODES = {"p": _P, "i": _I, "l": _L, "f": _F, "u": _U}
-
-# name -> (restype code, argument codes); order and meaning exactly as in include/mickey_hip.h
-SIGNATURES = {
-    "mk_version": ("i", ""),
-    "mk_last_error": ("s", ""),
-    "mk_preprocess_u8": ("i", "pliiipiip"),
-    "mk_gemm": ("i", "pipippiiiiiiip"),
-    "mk_gemm_grouped": ("i", "pilpilplpiliiiiiiip"),
-    "mk_gemm_ls_residual": ("i", "pipipppiiiiip"),
-    "mk_gemm_qkv": ("i", "pipippppiiiifip"),
-    "mk_gemm_patch_embed": ("i", "pipipppiiiiip"),
-    "mk_gemm_ls_residual_ln": ("i", "pipippppipppiiiiip"),
-    "mk_gemm_patch_embed_ln": ("i", "pipipppppiiiiip"),
-    "mk_cls_token_ln": ("i", "pppppiiiip"),
-    "mk_recentre_split": ("i", "ppplilp"),
-    "mk_gemm_ln": ("i", "pipipppfppiiiiiip"),
-    "mk_gemm_qkv_ln": ("i", "pipipppfppppiiiifip"),
-    "mk_im2col_patch14": ("i", "plliiiipiip"),
-    "mk_cls_token": ("i", "pppiiip"),
-    "mk_layernorm": ("i", "pippfpiipiiiiiiiiiip"),
-    "mk_layernorm_nchw": ("i", "pippfpiiiiiip"),
-    "mk_gemm_ln128": ("i", "pilpilppfpipiiiiiiip"),
-    "mk_layernorm_planes": ("i", "pippfppifpiiiiiiiiipp"),
-    "mk_flash_attn_fwd": ("i", "ppppiiiiiip"),
-    "mk_bordered_rows": ("l", "iii"),
-    "mk_conv3x3": ("i", "pliplipilplplpiliiiiiiip"),
-    "mk_conv3x3_split": ("i", "pplipplipilplppiliiiiiiffpp"),
-    "mk_conv3x3_split_dscale": ("i", "ppipipiiiipp"),
-    "mk_split_planes": ("i", "plilfpplpp"),
-    "mk_absmax_scale_work_floats": ("l", ""),
-    "mk_absmax_scale": ("i", "piiiillllppp"),
-    "mk_conv_train_lead_rows": ("l", "i"),
-    "mk_conv_train_plane_rows": ("l", "iii"),
-    "mk_conv_train_planes": ("i", "plllliiiipppip"),
-    "mk_conv_train_weight_planes": ("i", "piiippppp"),
-    "mk_conv_wgrad_work_floats": ("l", "iiiii"),
-    "mk_conv_wgrad": ("i", "ppippiiiiippppp"),
-    "mk_gemm_grouped_split": ("i", "ppilpilplppiliiiiiffpp"),
-    "mk_posenc_add": ("i", "ppppiiiiiip"),
-    "mk_linattn_work_floats": ("l", "iiii"),
-    "mk_linattn_kv": ("i", "pppiiiip"),
-    "mk_linattn_apply": ("i", "pppiiiiiip"),
-    "mk_linattn_kv_fused": ("i", "pilpilppiiiiip"),
-    "mk_linattn_apply_fused": ("i", "pilpilppilppfpiliiiiip"),
-    "mk_linattn_train_work_floats": ("l", "iiii"),
-    "mk_linattn_train_fwd": ("i", "pllpllpllfpppiiiip"),
-    "mk_linattn_train_bwd": ("i", "pllpllpllppfpppppiiiip"),
-    "mk_train_rows_per_chunk": ("i", "i"),
-    "mk_train_chunks": ("i", "i"),
-    "mk_train_ln_steps": ("i", "i"),
-    "mk_train_linear_fwd": ("i", "pliplipppipliiip"),
-    "mk_train_linear_ln128_fwd": ("i", "pliplipppfplpppip"),
-    "mk_train_linear_dgrad": ("i", "pllipppiplplipliiiip"),
-    "mk_train_linear_wgrad": ("i", "pllipliplipliiiip"),
-    "mk_train_tail": ("i", "plilplilpp"),
-    "mk_train_ln128_fwd": ("i", "pppfplpppip"),
-    "mk_train_ln128_bwd": ("i", "pppppplip"),
-    "mk_train_headtail_chunk_rows": ("i", ""),
-    "mk_train_headtail_chunks": ("i", "l"),
-    "mk_train_headtail_fwd": ("i", "pppiiiiiififfp"),
-    "mk_train_headtail_bwd": ("i", "ppppppppiiiiiffp"),
-    "mk_train_desc_l2norm_fwd": ("i", "pppiiifp"),
-    "mk_train_desc_l2norm_bwd": ("i", "ppppiiip"),
-    "mk_train_bn_chunk_rows": ("i", ""),
-    "mk_train_bn_chunks": ("i", "l"),
-    "mk_train_bn_work_floats": ("l", "li"),
-    "mk_train_bn_fwd": ("i", "plppplpppffpplpppiiiip"),
-    "mk_train_bn_bwd": ("i", "plplpppppplplppfiiip"),
-    "mk_optim_chunk_elems": ("i", ""),
-    "mk_optim_chunks": ("l", "l"),
-    "mk_optim_grad_stats": ("i", "pipipp"),
-    "mk_optim_reduce": ("i", "pifpp"),
-    "mk_optim_adam": ("i", "pipipp"),
-    "mk_head_tails": ("i", "pppppppppppiiiiiiiififp"),
-    "mk_dual_softmax_work_floats": ("l", "iiii"),
-    "mk_dual_softmax": ("i", "ppppfifppppiiiip"),
-    "mk_dual_softmax_split_work_floats": ("l", "iii"),
-    "mk_dual_softmax_split": ("i", "ppppfifppppiiiip"),
-    "mk_sinkhorn_work_floats": ("l", "iii"),
-    "mk_sinkhorn": ("i", "ppppfippppiiiip"),
-    "mk_dual_softmax_kf": ("i", "ppppfifppppiiiipip"),
-    "mk_dual_softmax_split_kf": ("i", "ppppfifppppiiiipip"),
-    "mk_sinkhorn_kf": ("i", "ppppfippppiiiipip"),
-    "mk_dual_softmax_pairs": ("i", "ppppfifppppiiiippiip"),
-    "mk_dual_softmax_split_pairs_work_floats": ("l", "iiiiii"),
-    "mk_dual_softmax_split_pairs": ("i", "ppppfifppppiiiippiip"),
-    "mk_sinkhorn_pairs": ("i", "ppppfippppiiiippiip"),
-    "mk_dsc_split_planes_floats": ("l", "ii"),
-    "mk_dsc_split_planes": ("i", "ppiiip"),
-    "mk_dual_softmax_split_planes_work_floats": ("l", "iii"),
-    "mk_dual_softmax_split_planes": ("i", "ppppfifppppiiippiip"),
-    "mk_mutual_nn": ("i", "ppppiiip"),
-    "mk_dual_softmax_train_work_floats": ("l", "iiii"),
-    "mk_dual_softmax_train": ("i", "ppppfppppppiiiiip"),
-    "mk_dual_softmax_bwd_work_floats": ("l", "iiii"),
-    "mk_dual_softmax_bwd": ("i", "ppppfpppppppppiiiiip"),
-    "mk_exprace_topk_work_bytes": ("l", "iiil"),
-    "mk_exprace_topk_state_bytes": ("l", "ii"),
-    "mk_exprace_topk": ("i", "ppuupppppiiliip"),
-    "mk_counter_add": ("i", "pup"),
-    "mk_gather_backproject": ("i", "ppppppppppppiiiiip"),
-    "mk_gather_backproject_kf": ("i", "ppppppppppppiiiiipip"),
-    "mk_gather_backproject_pairs": ("i", "ppppppppppppiiiiippiip"),
-    "mk_gather_backproject_bwd": ("i", "ppppppppppiiiiip"),
-    "mk_ransac_hypotheses": ("i", "pppppuupfppppiiilp"),
-    "mk_refine_pose": ("i", "pppppfiipppppppiiiip"),
-    "mk_pose_finalize": ("i", "ppppip"),
-    "mk_train_ransac_masks": ("i", "pppppuupfiipppiiilp"),
-    "mk_reinforce_scatter": ("i", "ppppiiilp"),
-    "mk_train_tail_fwd": ("i", "pppppppiiiifiifpppp"),
-    "mk_train_tail_bwd": ("i", "pppppppiiiifiifppppppp"),
-    "mk_train_aggregate_fwd": ("i", "pppiiififfppppp"),
-    "mk_train_aggregate_bwd": ("i", "ppiiipp"),
-}
-
-# development knobs (include/mickey_hip_dev.h): process-wide schedule selectors for benchmarks / tests, never called by
-# the product path
-DEV_SIGNATURES = {
-    "mk_gemm_set_tile": ("i", "i"),
-    "mk_attn_set_mode": ("i", "i"),
-    "mk_dev_mfma_sustained": ("i", "piiip"),
-}
-
-_lib = None
-_missing = set()
-
 
 class MickeyHipError(RuntimeError):
     pass
+
+
+# every type the headers may use; widening this set is a deliberate edit here (INTEGRATION.md section 2)
+_SCALARS = {"int": "i", "long long": "l", "float": "f", "unsigned long long": "u"}   # any pointer and mk_stream_t: "p"
+_FIELDS = {"long long": "q", "double": "d"}                                          # struct fields; any pointer: "q"
+_CODES = {"p": ctypes.c_void_p, "i": ctypes.c_int, "l": ctypes.c_longlong, "f": ctypes.c_float, "u": ctypes.c_ulonglong,
+          "s": ctypes.c_char_p}
+_TYPE_WORDS = {"void", "char", "short", "int", "long", "float", "double", "signed", "unsigned", "const", "mk_stream_t"}
+
+Header = collections.namedtuple("Header", "signatures params constants structs")
+
+
+def _bad(what, stmt):
+    return MickeyHipError("mickey_hip headers: %s in `%s`" % (what, " ".join(stmt.split())))
+
+
+def _ctype(text, stmt):
+    """a C type as written -> (its words without const, whether it is a pointer)"""
+    m = re.fullmatch(r"\s*((?:\w+\s+)*\w+)\s*((?:\*\s*)*)", text)
+    if not m:
+        raise _bad("unreadable type `%s`" % text.strip(), stmt)
+    return " ".join(w for w in m.group(1).split() if w != "const"), bool(m.group(2))
+
+
+def _code(text, stmt, table):
+    base, pointer = _ctype(text, stmt)
+    if pointer:
+        return "q" if table is _FIELDS else "p"
+    if base == "mk_stream_t" and table is _SCALARS:
+        return "p"
+    if base not in table:
+        raise _bad("type `%s` outside the binding's set" % text.strip(), stmt)
+    return table[base]
+
+
+def _declarator(text, stmt):
+    """`const float* x` -> (`const float*`, `x`); a declaration without a name raises"""
+    m = re.fullmatch(r"\s*(.*[\s*])(\w+)\s*", text, re.S)
+    if not m or m.group(2) in _TYPE_WORDS:
+        raise _bad("parameter `%s` without a name" % text.strip(), stmt)
+    return m.group(1), m.group(2)
+
+
+def parse_header(text):
+    """The declarations of a mickey_hip header -> Header(signatures {name: (result code, argument codes)}, params {name:
+    parameter names}, constants {MK_*: int} (enumerators and #defines), structs {name: [(field, struct-module code)]}).
+    Anything but enum blocks, `typedef struct`s, the mk_stream_t typedef and `ret mk_name(params);` prototypes raises."""
+    signatures, params, constants, structs = {}, {}, {}, {}
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    for line, name, value in re.findall(r"^([ \t]*#[ \t]*define[ \t]+(MK_\w+)\b(.*))$", text, re.M):
+        if not re.fullmatch(r"\s+-?\d+\s*", value) or name in constants:
+            raise _bad("not a new #define MK_NAME n", line)
+        constants[name] = int(value)
+    text = re.sub(r"^[ \t]*#[^\n]*$", "", text, flags=re.M)
+    text = re.sub(r'extern\s+"C"\s*\{(.*)\}\s*$', r"\1", text, flags=re.S)
+
+    def enum(m):
+        for item in filter(None, (s.strip() for s in m.group(1).split(","))):
+            e = re.fullmatch(r"(MK_\w+)\s*=\s*(-?\d+)", item)
+            if not e or e.group(1) in constants:
+                raise _bad("enumerator `%s` is not a new MK_NAME = n" % item, m.group(0))
+            constants[e.group(1)] = int(e.group(2))
+        return ""
+
+    def struct(m):
+        fields = []
+        for stmt in filter(None, (s.strip() for s in m.group(2).split(";"))):
+            first, *more = stmt.split(",")
+            base, name = _declarator(first, stmt)
+            fields.append((name, _code(base, stmt, _FIELDS)))
+            base = base.rstrip("* \t\n")   # `float *p, *g`: the stars belong to each name
+            for decl in more:
+                d = re.fullmatch(r"\s*(\**)\s*(\w+)\s*", decl)
+                if not d:
+                    raise _bad("unreadable field `%s`" % decl.strip(), stmt)
+                fields.append((d.group(2), _code(base + d.group(1), stmt, _FIELDS)))
+        if m.group(1) in structs or len({f for f, _ in fields}) != len(fields):
+            raise _bad("duplicate declaration", m.group(0))
+        structs[m.group(1)] = fields
+        return ""
+
+    text = re.sub(r"\benum\s*\{([^{}]*)\}\s*;", enum, text)
+    text = re.sub(r"\btypedef\s+struct\s+(\w+)\s*\{([^{}]*)\}\s*\1\s*;", struct, text)
+    text = re.sub(r"\btypedef\s+void\s*\*\s*mk_stream_t\s*;", "", text)
+    *stmts, rest = text.split(";")
+    if rest.strip():
+        raise _bad("unterminated statement", rest)
+    for stmt in stmts:
+        m = re.fullmatch(r"\s*([\w\s*]+?[\s*])(mk_\w+)\s*\(([^()]*)\)\s*", stmt, re.S)
+        if not m:
+            raise _bad("not a prototype `ret mk_name(params)`", stmt)
+        ret, name, plist = m.groups()
+        if name in signatures:
+            raise _bad("duplicate declaration", stmt)
+        res = "s" if _ctype(ret, stmt) == ("char", True) and "const" in ret.split() else _code(ret, stmt, _SCALARS)
+        decls = [] if plist.strip() in ("", "void") else [_declarator(p, stmt) for p in plist.split(",")]
+        signatures[name] = (res, "".join(_code(t, stmt, _SCALARS) for t, _ in decls))
+        params[name] = tuple(n for _, n in decls)
+    return Header(signatures, params, constants, structs)
+
+
+def _parse_file(name):
+    with open(os.path.join(_build.INCLUDE, name)) as f:
+        return parse_header(f.read())
+
+
+_ABI, _DEV = _parse_file("mickey_hip.h"), _parse_file("mickey_hip_dev.h")
+for _kind in ("signatures", "constants", "structs"):
+    _twice = set(getattr(_ABI, _kind)) & set(getattr(_DEV, _kind))
+    if _twice:
+        raise MickeyHipError("mickey_hip headers: %s declared in both headers" % sorted(_twice))
+
+# name -> (restype code, argument codes); order and meaning exactly as in include/mickey_hip.h
+SIGNATURES = _ABI.signatures
+# development knobs (include/mickey_hip_dev.h): process-wide schedule selectors for benchmarks / tests, never called by
+# the product path
+DEV_SIGNATURES = _DEV.signatures
+PARAM_NAMES = {**_ABI.params, **_DEV.params}
+CONSTANTS = {**_ABI.constants, **_DEV.constants}   # every MK_* enumerator and #define, also a module attribute of its C name
+STRUCTS = {**_ABI.structs, **_DEV.structs}
+globals().update(CONSTANTS)
+
+MK_BF16, MK_F16, MK_F32 = (CONSTANTS[k] for k in ("MK_BF16", "MK_F16", "MK_F32"))   # (spelled out: dtype_code names them)
+ACT_NONE, ACT_RELU, ACT_GELU = (CONSTANTS[k] for k in ("MK_ACT_NONE", "MK_ACT_RELU", "MK_ACT_GELU"))
+
+_lib = None
+_missing = set()
 
 
 def lib_path():
@@ -166,7 +167,7 @@ def load():
         except AttributeError:
             _missing.add(name)  # reported by missing_symbols(); calling it raises
             continue
-        fn.restype = ctypes.c_char_p if res == "s" else _CODES[res]
+        fn.restype = _CODES[res]
         fn.argtypes = [_CODES[c] for c in args]
     _lib = lib
     return lib
@@ -203,15 +204,26 @@ def dtype_code(dt):
     raise MickeyHipError("unsupported low-precision dtype %s" % dt)
 
 
+def _exported(lib, name):
+    if name in _missing:
+        raise MickeyHipError("libmickey_hip.so does not export %s (stale build?)" % name)
+    return getattr(lib, name)
+
+
 def call(name, *args):
     """Call an ABI function that returns a status code; raise on failure."""
     lib = load()
-    if name in _missing:
-        raise MickeyHipError("libmickey_hip.so does not export %s (stale build?)" % name)
-    rc = getattr(lib, name)(*args)
+    try:
+        rc = _exported(lib, name)(*args)
+    except ctypes.ArgumentError as e:   # ctypes says "argument 13: TypeError: ...": name the C parameter
+        m = re.match(r"argument (\d+)(.*)", str(e), re.S)
+        names = PARAM_NAMES.get(name, ())
+        if not m or not 0 < int(m.group(1)) <= len(names):
+            raise
+        raise MickeyHipError("%s: argument %s '%s'%s" % (name, m.group(1), names[int(m.group(1)) - 1], m.group(2))) from None
     if rc != 0:
         raise MickeyHipError("%s failed (%d): %s" % (name, rc, lib.mk_last_error().decode()))
 
 
 def query(name, *args):
-    return getattr(load(), name)(*args)
+    return _exported(load(), name)(*args)

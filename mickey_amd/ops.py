@@ -6,6 +6,7 @@ import numpy as np
 import torch
 
 
+from . import _native
 from ._native import ACT_GELU, ACT_NONE, ACT_RELU, call, dtype_code, ptr, query, stream  # noqa: F401
 
 LOG2E = 1.4426950408889634
@@ -208,7 +209,7 @@ def flash_attn(q, k, vt, out, nimg, heads, ntok, ntok_pad):
     return out
 
 
-CONV_OUT_DENSE, CONV_OUT_BORDERED, CONV_OUT_F32 = 0, 1, 2
+CONV_OUT_DENSE, CONV_OUT_BORDERED, CONV_OUT_F32 = _native.MK_CONV_OUT_DENSE, _native.MK_CONV_OUT_BORDERED, _native.MK_CONV_OUT_F32
 
 
 def bordered_rows(nimg, H, W):
@@ -582,7 +583,8 @@ def train_ln128_bwd(g, xhat, rstd, gamma, gu=None, part=None, part_stride=256):
 
 # ---- training: the head tails (mickey_hip.h: mk_train_headtail_* / mk_train_desc_l2norm_*; train_tails.py).  Features are 2-D fp32
 # [nimg h w, C] tensors with dense, 16-byte aligned rows; outputs may be passed in (tests place them in guarded windows). ----------
-TAIL_IDENTITY, TAIL_SIGMOID, TAIL_MASKED_SIGMOID, TAIL_SOFTMAX = 0, 1, 2, 3
+TAIL_IDENTITY, TAIL_SIGMOID, TAIL_MASKED_SIGMOID, TAIL_SOFTMAX = (_native.MK_TAIL_IDENTITY, _native.MK_TAIL_SIGMOID,
+                                                                  _native.MK_TAIL_MASKED_SIGMOID, _native.MK_TAIL_SOFTMAX)
 HEADTAIL_CHUNK_ROWS = 208   # rows of one weight-gradient partial == mk_train_headtail_chunk_rows() (tests/test_train_tails_cpu.py)
 TAIL_MIN_C, TAIL_MAX_C = 4, 256
 

@@ -32,8 +32,8 @@ from . import _native
 from ._train_common import is_number, is_real
 
 CHUNK_ELEMS = 4096   # elements of one chunk == mk_optim_chunk_elems() (tests/test_train_optim_cpu.py)
-FLAG_NORM, FLAG_PARAM = 1, 2   # mickey_hip.h: MK_OPTIM_NORM, MK_OPTIM_PARAM
-_ROW = struct.Struct("=qqqqqqdddddq")   # mickey_hip.h: mk_optim_row
+FLAG_NORM, FLAG_PARAM = _native.MK_OPTIM_NORM, _native.MK_OPTIM_PARAM
+_ROW = struct.Struct("=" + "".join(code for _, code in _native.STRUCTS["mk_optim_row"]))   # mickey_hip.h's fields, in order
 ROW_WORDS = _ROW.size // 8
 _REFUSED = ("amsgrad", "maximize", "capturable", "differentiable", "decoupled_weight_decay")
 

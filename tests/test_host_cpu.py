@@ -373,3 +373,137 @@ def test_features_lp_resolution():
     c["AMD"]["FEATURES_LP"] = "sometimes"
     with pytest.raises(ValueError):
         resolve_features_lp(c, torch.float16)
+
+
+# ---- the binding is derived from the headers (mickey_amd/_native.py: parse_header) --------------------------------------------
+_ABI_PROBE = r"""
+#include <cstdio>
+#include <type_traits>
+#include "mickey_hip.h"
+#include "mickey_hip_dev.h"
+template <class T> constexpr char code(bool result) {
+  return result && std::is_same<T, const char*>::value ? 's'
+       : std::is_pointer<T>::value ? 'p'
+       : std::is_same<T, int>::value ? 'i'
+       : std::is_same<T, long long>::value ? 'l'
+       : std::is_same<T, float>::value ? 'f'
+       : std::is_same<T, unsigned long long>::value ? 'u' : '?';
+}
+template <class R, class... A> void show(const char* name, R (*)(A...)) {
+  const char args[] = {code<A>(false)..., 0};
+  std::printf("%s %c %s\n", name, code<R>(true), args);
+}
+int main() {
+@SHOWS@
+  return 0;
+}
+"""
+
+
+def _host_cxx():
+    """the first of c++ on PATH and the clang++ that hipcc drives (present wherever the library can be built)"""
+    import shutil
+    from mickey_amd import build
+    hipcc = shutil.which(build.hipcc()) or build.hipcc()
+    bindir = os.path.dirname(os.path.realpath(hipcc))
+    for c in (shutil.which("c++"), os.path.join(bindir, "clang++"), os.path.join(bindir, "..", "lib", "llvm", "bin", "clang++"),
+              os.path.join(os.path.dirname(hipcc), "..", "lib", "llvm", "bin", "clang++")):
+        if c and os.path.exists(c):
+            return c
+    pytest.fail("no host C++ compiler: neither c++ on PATH nor a clang++ beside %s" % hipcc)
+
+
+def test_abi_binding_matches_the_compilers_view(tmp_path):
+    """Every letter code of SIGNATURES / DEV_SIGNATURES against what a C++ compiler makes of the same headers: decltype(&mk_name)
+    taken apart with <type_traits>.  Types only -- nothing is linked -- and no regular expression shared with the parser."""
+    import subprocess
+    from mickey_amd import _native
+    table = {**_native.SIGNATURES, **_native.DEV_SIGNATURES}
+    assert len(table) == len(_native.SIGNATURES) + len(_native.DEV_SIGNATURES) > 100
+    src, exe = tmp_path / "abi_probe.cpp", tmp_path / "abi_probe"
+    src.write_text(_ABI_PROBE.replace("@SHOWS@", "\n".join('  show("%s", static_cast<decltype(&%s)>(nullptr));' % (n, n) for n in table)))
+    subprocess.run([_host_cxx(), "-std=c++17", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
+    out = subprocess.run([str(exe)], check=True, stdout=subprocess.PIPE, text=True).stdout
+    seen = {}
+    for line in out.splitlines():
+        name, res, *args = line.split(" ")
+        seen[name] = (res, "".join(args))
+    assert set(seen) == set(table)
+    for name in table:
+        assert seen[name] == table[name], (name, seen[name], table[name])
+        assert len(_native.PARAM_NAMES[name]) == len(table[name][1]) and all(_native.PARAM_NAMES[name]), name
+
+
+def test_abi_parser_is_strict():
+    from mickey_amd import _native
+    P, E = _native.parse_header, _native.MickeyHipError
+    ok = P('#ifdef __cplusplus\nextern "C" {\n#endif\ntypedef void* mk_stream_t; /* a stream */\nenum { MK_A = 0, MK_B = 3 };\n'
+           "#define MK_C 7\ntypedef struct mk_row { float *p, *g; long long n; double lr; } mk_row;\n"
+           "const char* mk_text(void);\nlong long mk_f(const char* name, const unsigned char* src, unsigned long long seed,\n"
+           "                  float eps, long long n, int k, mk_stream_t stream);\n#ifdef __cplusplus\n}\n#endif\n")
+    assert ok.signatures == {"mk_text": ("s", ""), "mk_f": ("l", "ppuflip")}   # a const char* PARAMETER is a pointer
+    assert ok.params["mk_f"] == ("name", "src", "seed", "eps", "n", "k", "stream") and ok.params["mk_text"] == ()
+    assert ok.constants == {"MK_A": 0, "MK_B": 3, "MK_C": 7}
+    assert ok.structs == {"mk_row": [("p", "q"), ("g", "q"), ("n", "q"), ("lr", "d")]}
+    for bad, quoted in (("int mk_f(short n);", "short n"),                                   # a scalar outside the set
+                        ("int mk_f(unsigned n);", "unsigned n"),
+                        ("short mk_f(int n);", "short mk_f"),
+                        ("void mk_f(int n);", "void mk_f"),
+                        ("int mk_f(int n, float);", "float"),                                # parameters without a name
+                        ("int mk_f(const float*, int n);", "const float*"),
+                        ("int mk_f(long long);", "long long"),
+                        ("int mk_f(int n);\nint mk_f(int n);", "mk_f"),                      # a duplicate prototype
+                        ("enum { MK_A = 0 };\nenum { MK_A = 1 };", "MK_A"),
+                        ("#define MK_A 0\nenum { MK_A = 1 };", "MK_A"),
+                        ("#define MK_A (1 << 2)\nint mk_f(int n);", "MK_A"),                 # constants are plain integers
+                        ("enum { MK_A, MK_B };", "MK_A"),
+                        ("int mk_f(int n);\nint mk_count;", "mk_count"),                     # statements that are no prototype
+                        ("typedef int mk_int;\nint mk_f(int n);", "typedef int mk_int"),
+                        ("int mk_f(int n);\nstatic int helper(void);", "helper"),
+                        ("int mk_f(int (*cb)(int));", "cb"),
+                        ("int mk_f(int n)", "mk_f"),                                         # (no terminating semicolon)
+                        ("typedef struct mk_row { float* p; int flags; } mk_row;", "int flags"),   # a struct field of unknown type
+                        ("typedef struct mk_row { float x; } mk_row;", "float x")):
+        with pytest.raises(E) as err:
+            P(bad)
+        assert quoted in str(err.value), (bad, str(err.value))
+
+
+def test_abi_recentre_split_rows_are_long_long():
+    """the one entry the hand-written table had wrong: (..., long long rows, int D, int dtype, stream)"""
+    from mickey_amd import _native
+    assert _native.SIGNATURES["mk_recentre_split"] == ("i", "pppliip")
+    assert _native.PARAM_NAMES["mk_recentre_split"] == ("xh", "xl", "stats", "rows", "D", "dtype", "stream")
+
+
+def test_abi_constants_come_from_the_headers():
+    from mickey_amd import _native, ops, train_optim
+    found = {}
+    for h in ("mickey_hip.h", "mickey_hip_dev.h"):
+        raw = open(os.path.join(ROOT, "include", h)).read()
+        found.update((k, int(v)) for k, v in re.findall(r"\b(MK_[A-Z0-9_]+) = (\d+)", raw) + re.findall(r"#define (MK_[A-Z0-9_]+) (\d+)", raw))
+    assert len(found) >= 22 and found == _native.CONSTANTS
+    for name, value in found.items():
+        assert getattr(_native, name) is _native.CONSTANTS[name] and getattr(_native, name) == value, name
+    for mod, alias, c_name in [(_native, "MK_" + k, "MK_" + k) for k in ("BF16", "F16", "F32")] + \
+            [(m, "ACT_" + k, "MK_ACT_" + k) for m in (_native, ops) for k in ("NONE", "RELU", "GELU")] + \
+            [(ops, "CONV_OUT_" + k, "MK_CONV_OUT_" + k) for k in ("DENSE", "BORDERED", "F32")] + \
+            [(ops, "TAIL_" + k, "MK_TAIL_" + k) for k in ("IDENTITY", "SIGMOID", "MASKED_SIGMOID", "SOFTMAX")] + \
+            [(train_optim, "FLAG_" + k, "MK_OPTIM_" + k) for k in ("NORM", "PARAM")]:
+        assert getattr(mod, alias) is _native.CONSTANTS[c_name], (mod.__name__, alias)
+    # the values the kernels were built against
+    assert (_native.MK_BF16, _native.MK_F16, _native.MK_F32) == (0, 1, 2) and (ops.ACT_NONE, ops.ACT_RELU, ops.ACT_GELU) == (0, 1, 2)
+    assert (ops.CONV_OUT_DENSE, ops.CONV_OUT_BORDERED, ops.CONV_OUT_F32) == (0, 1, 2)
+    assert (ops.TAIL_IDENTITY, ops.TAIL_SIGMOID, ops.TAIL_MASKED_SIGMOID, ops.TAIL_SOFTMAX) == (0, 1, 2, 3)
+    assert (train_optim.FLAG_NORM, train_optim.FLAG_PARAM) == (1, 2)
+    assert train_optim._ROW.format == "=qqqqqqdddddq" and [f for f, _ in _native.STRUCTS["mk_optim_row"]] == \
+        ["p", "g", "m", "v", "step", "numel", "lr", "beta1", "beta2", "eps", "weight_decay", "flags"]
+
+
+def test_abi_call_names_the_c_parameter_and_query_checks_exports(nv, monkeypatch):
+    with pytest.raises(nv.MickeyHipError, match=r"mk_layernorm: argument 13 'rows_per_img'"):
+        nv.call("mk_layernorm", None, 0, None, None, 1e-6, None, 0, 0, None, 0, 0, 0, "seven", 0, 0, 0, 0, 0, 0, None)
+    monkeypatch.setattr(nv, "_missing", {"mk_bordered_rows"})   # a stale library: the symbol is declared, not exported
+    for fn in (nv.call, nv.query):
+        with pytest.raises(nv.MickeyHipError, match="does not export mk_bordered_rows"):
+            fn("mk_bordered_rows", 1, 1, 1)
