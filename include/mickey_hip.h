@@ -863,6 +863,44 @@ int mk_train_aggregate_bwd(const float* coef, const float* g_pair, int B, int it
 int mk_reinforce_scatter(const int* idx, const float* loss_value, float* gradients, float* gradients_b, int B,
                          int it_matches, int S, long long ncell, mk_stream_t stream);
 
+/* ---- validation on the device (mk_metrics.hip) ---------------------------------------------------------------------------
+ * The per-pair metrics of a validation step (reference lib/utils/metrics.py:12-53 pose_error_torch and :83-125 vcre_torch, as
+ * lib/models/MicKey/model.py:76-85 calls them): one launch, one wave per pair, fp64 arithmetic from the fp32 inputs, every
+ * result rounded once to fp32.  For pair b of R [B, 9], t [B, 3], T_gt [B, 16] (the 4 x 4 T_0to1, row-major: Rgt, tgt),
+ * K [B, 9] (Kori_color0), conf [B] (the solver's soft inlier count; NULL: 0) the record
+ *   records[(row0 + b) * 8 ..] = (t_err_ang, t_err_scale, t_err_scale_sym, t_err_euc, R_err, vcre, conf, 0)
+ *   t_err_ang        a = deg acos(clip(<t, tgt> / (|t| |tgt| + 1e-9), -1, 1)),  min(a, 180 - a)
+ *   t_err_scale      |t| / |tgt|;   t_err_scale_sym  max(|t| / |tgt|, |tgt| / |t|);   t_err_euc  |t - tgt|
+ *   R_err            deg acos(clip((trace(R^T Rgt) - 1) / 2, -1, 1))
+ *   vcre             mean over the 196 eye-grid points e of sqrt(du^2 + dv^2 + 1e-6), (du, dv) = clip(proj(K, e)) -
+ *                    clip(proj(K, Rgt^T (R e + t - tgt))), proj divides by z + 1e-16, u clipped to [0, W], v to [0, H]
+ *                    (the residual is inv(cam2w_gt) cam2w_est, the direction of vcre_torch, in closed form)
+ * A NaN input comes out as NaN (torch.clip / minimum / maximum semantics), in its pair's record only.  records float32
+ * [capacity, 8], 16-byte aligned; rows outside [row0, row0 + B) are not written.  B >= 1, row0 >= 0, row0 + B <= capacity. */
+int mk_pose_metrics(const float* R, const float* t, const float* T_gt, const float* K, const float* conf, float W, float H,
+                    float* records, long long row0, int B, long long capacity, mk_stream_t stream);
+
+/* The summary of a validation epoch (reference lib/models/MicKey/model.py:205-280 on_validation_epoch_end with
+ * lib/benchmarks/utils.py:138-188 precision_recall, three times on the host there): two launches, no atomics, no sort, sums
+ * in a fixed order (bit-identical from run to run).  records float32 [N, 8] as mk_pose_metrics writes them; three acceptance
+ * tests (strict, as the trainer): t_err_euc < th_t and R_err < th_R | t_err_euc < th_t2 and R_err < th_R2 | vcre < th_px.
+ * Average precision without a sort:  AP = 1 / (N + failures) * sum_i cumTP_i / cumN_i  with  cumN_i = #{j : c_j >= c_i},
+ * cumTP_i = #{j : c_j >= c_i and tp_j} (integers; the quotient and the sums fp64): every group of tied confidences contributes
+ * count * precision / (N + failures), which is precision_recall's sum of recall steps times precisions.  A confidence that is
+ * not finite ranks as -inf and is counted in out[1]; a NaN metric makes its mean NaN and its acceptance false.
+ *   out float32 [16] = (N, records with a non-finite confidence, mean t_err_ang, mean t_err_euc, mean R_err, mean vcre,
+ *                       prec_pose, auc_pose, prec_pose_10, auc_pose_10, prec_vcre, auc_vcre,
+ *                       mean loss, mean loss_R, mean loss_t, 0),   precisions = accepted / (N + failures)
+ *   losses float32 [S, 3] (loss, loss_R, loss_t of the S validation steps) or NULL with S = 0 (the three means are then 0)
+ *   work   double [mk_pose_summary_work_doubles(N)]: row k < ceil(N / tile) the partial sums of workgroup k, the last row the
+ *          16 values of `out` before their rounding to fp32.
+ * The ranking is quadratic: every record is compared with every record, in LDS tiles of mk_pose_summary_tile() records.
+ * 1 <= N <= 2^18 (6.9e10 compares), failures >= 0. */
+int mk_pose_summary_tile(void);
+long long mk_pose_summary_work_doubles(int N);
+int mk_pose_summary(const float* records, int N, int failures, float th_t, float th_R, float th_t2, float th_R2, float th_px,
+                    const float* losses, int S, float* out, double* work, mk_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

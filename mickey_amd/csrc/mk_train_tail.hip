@@ -23,6 +23,7 @@
 // The rigid-fit arithmetic (Jacobi sweeps, column completion, Procrustes moments, 3x3 products) is mk_procrustes.hpp, shared with
 // mk_solver.hip; this file sets no contraction pragma, so here it compiles fused (see the head of that header).
 #include "mk_common.hpp"
+#include "mk_eye_grid.hpp"
 #include "mk_procrustes.hpp"
 
 namespace {
@@ -73,13 +74,7 @@ __device__ void svd3(const double* Hin, double* U, double* S, double* V) {
   }
 }
 
-// ---- the eye grid of the VCRE (lib/benchmarks/reprojection.py:34-58): point p of 196 ------------------------------------
-__device__ __forceinline__ void eye_point(int p, float* e) {
-  const int k = p % 7, i = (p / 7) % 7, j = p / 49;
-  e[0] = ((float)i - 3.0f) * 0.3f;
-  e[1] = ((float)j - 1.5f) * 0.3f;
-  e[2] = (float)k * 0.3f + 1.8f;
-}
+// ---- the VCRE over the eye grid (mk_eye_grid.hpp: point p of 196) -----------------------------------------------------------
 __device__ __forceinline__ void proj2(const float* K, const float* P, float* uv, float* q) {
 #pragma unroll
   for (int a = 0; a < 3; ++a) q[a] = K[a * 3] * P[0] + K[a * 3 + 1] * P[1] + K[a * 3 + 2] * P[2];

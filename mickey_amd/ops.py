@@ -1204,3 +1204,35 @@ def refine_pose(X, Y, Rh, th, score, B, it_matches, it_ransac, th_inlier, num_re
     if finalize:
         call("mk_pose_finalize", ptr(R), ptr(t), ptr(conf), ptr(invalid), B, stream())
     return R, t, conf, best, mask, rounds, invalid
+
+
+def pose_metrics(R, t, T_gt, K, conf, W, H, records, row0=0):
+    """mk_pose_metrics: the records of the B pairs of R [B, 3, 3], t [B, 1, 3], T_gt [B, 4, 4], K [B, 3, 3], conf [B] (or None) into
+    rows row0 .. row0 + B of records fp32 [capacity, 8] (in place; returns records)."""
+    R, t, T_gt, K, conf = _c(R, t, T_gt, K, conf)
+    _chk(records, torch.float32)
+    call("mk_pose_metrics", ptr(R), ptr(t), ptr(T_gt), ptr(K), ptr(conf), float(W), float(H), ptr(records), int(row0),
+         int(R.shape[0]), int(records.shape[0]), stream())
+    return records
+
+
+def pose_summary_tile():
+    """Records of an LDS tile of mk_pose_summary's ranking launch."""
+    return int(query("mk_pose_summary_tile"))
+
+
+def pose_summary(records, N, failures, thresholds, losses=None, S=0, out=None, work=None):
+    """mk_pose_summary over the first N rows of records fp32 [*, 8] (and the first S rows of losses fp32 [*, 3], or None) ->
+    (out fp32 [16], work fp64 [ceil(N / tile) + 1, 16]: the partial rows, then the 16 results before their rounding)."""
+    _chk(records, torch.float32)
+    dev = records.device
+    if losses is not None:
+        _chk(losses, torch.float32)
+    if out is None:
+        out = torch.empty((16,), device=dev, dtype=torch.float32)
+    if work is None:
+        work = torch.empty((int(query("mk_pose_summary_work_doubles", int(N))) // 16, 16), device=dev, dtype=torch.float64)
+    th = [float(v) for v in thresholds]
+    call("mk_pose_summary", ptr(records), int(N), int(failures), th[0], th[1], th[2], th[3], th[4], ptr(losses), int(S), ptr(out),
+         ptr(work), stream())
+    return out, work
