@@ -58,6 +58,28 @@ def guarded(rows, cols, dtype, device, ld=None, fill=None):
     return view, check
 
 
+def window(rows, cols, dev, shift=0):
+    """-> (flat fp32 view of rows * cols elements, check).  shift = 0: a guarded [rows, cols] window (256-byte aligned).  shift = 1 /
+    2: the same elements taken `shift` floats into a guarded [1, rows * cols + 2] window -- 4 / 8 bytes off every 16-byte boundary;
+    check() then also looks at the skipped elements in front of and behind the view."""
+    n = rows * cols
+    if shift == 0:
+        w, check = guarded(rows, cols, torch.float32, dev)
+        assert w.is_contiguous()
+        return w.view(-1), check
+    big, check0 = guarded(1, n + 2, torch.float32, dev)
+    view = big[0, shift:shift + n]
+    assert view.data_ptr() % 16 == 4 * shift
+    sent = sentinel_bits(torch.float32)
+
+    def check():
+        check0()
+        skipped = torch.cat([bits(big[0, :shift]), bits(big[0, shift + n:])])
+        assert skipped.numel() == 2 and bool((skipped == sent).all()), "an element next to a misaligned output was overwritten"
+
+    return view, check
+
+
 def vt_perm(t):
     """Column of V^T that holds token t: bits 2 and 3 of the token index swapped."""
     return (t & ~12) | ((t & 4) << 1) | ((t & 8) >> 1)

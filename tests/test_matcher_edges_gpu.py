@@ -18,6 +18,7 @@ import torch
 
 from tests.helpers import matcher_refs as R
 from tests.helpers.guarded import bits, guarded, sentinel_bits
+from tests.helpers.guarded import window as _window
 
 pytestmark = pytest.mark.gpu
 
@@ -48,27 +49,6 @@ def _nv():
 
 def _written(t):
     return not bool((bits(t) == SENT).any())
-
-
-def _window(rows, cols, dev, shift=0):
-    """-> (flat fp32 view of rows * cols elements, check).  shift = 0: a guarded [rows, cols] window (256-byte aligned).  shift = 1 /
-    2: the same elements taken `shift` floats into a guarded [1, rows * cols + 2] window -- 4 / 8 bytes off every 16-byte boundary;
-    check() then also looks at the skipped elements in front of and behind the view."""
-    n = rows * cols
-    if shift == 0:
-        w, check = guarded(rows, cols, torch.float32, dev)
-        assert w.is_contiguous()
-        return w.view(-1), check
-    big, check0 = guarded(1, n + 2, torch.float32, dev)
-    view = big[0, shift:shift + n]
-    assert view.data_ptr() % 16 == 4 * shift
-
-    def check():
-        check0()
-        skipped = torch.cat([bits(big[0, :shift]), bits(big[0, shift + n:])])
-        assert skipped.numel() == 2 and bool((skipped == SENT).all()), "an element next to a misaligned output was overwritten"
-
-    return view, check
 
 
 def _metric(kernel, family, got, ref64, floor, what):
